@@ -10,7 +10,7 @@ over the GPUs (GPU r renders pass r + N*k); the pass framebuffers are exchanged 
 1 GPU) and the finished slices are gathered to GPU 0.  By default the timed region is one
 full frame (strong scaling); `--steps K` times K passes per GPU (weak scaling).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scene teapot] [--no-sort]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scene teapot] [--no-sort] [--full] [--dump-outputs DIR]
     torchrun --nproc-per-node N bench.py --gpus N ...
 
 `--gpus N` is honoured however bench.py is started:
@@ -22,7 +22,11 @@ full frame (strong scaling); `--steps K` times K passes per GPU (weak scaling).
 Every line carries n_gpus = N and config.n_ranks_seen = the ranks the collective backend counted.
 
 Rank 0 prints ONE JSON line.  `value` = live ray segments (process_ray calls on live slots)
-per second over all GPUs, inputs resident in HBM.  `render_wall_ms` = one full frame (the
+per second over all GPUs, inputs resident in HBM; `ms_per_step` = the timed region / its steps.
+A plain run sets up, warms up, times the steps and prints the line.  `--dump-outputs DIR` also
+writes what the timed steps computed (DIR/framebuffer.npy, DIR/work_counts.npy; dump_outputs).
+
+`--full` adds the untimed legs; the fields below are null without it.  `render_wall_ms` = one full frame (the
 metric's second column); `bit_exact_vs_oracle` = this run's pass-0 framebuffer hashed against
 the oracle's (tests/golden/bench_pass0.json).  `roofline` prices the dominant kernel
 (trace_kernel) inside the timed step (its wave-residency share of a pass x ms_per_step):
@@ -592,8 +596,16 @@ def parse_args(argv=None):
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-counters", action="store_true", help="skip the byte-model counting rerun")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the untimed legs after the timed steps: exclusive pass and roofline, event-timed and "
+                         "counting reruns, the full-frame wall, parity hashes against the oracle, the CPU baseline "
+                         "(--no-counters / --no-cpu-baseline drop single legs)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="only the warmup and timed steps (profiling: --steps 1 --warmup 0 renders exactly one pass)")
+                    help="only the warmup and timed steps, the default without --full (profiling: --steps 1 --warmup 0 "
+                         "renders exactly one pass)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they left to the caller as DIR/<name>.npy: the "
+                         "framebuffer they accumulated (float32) and the work counts they returned (float64)")
     ap.add_argument("--dist", action="store_true", help="use the torch.distributed path even at N=1")
     ap.add_argument("--inlib", action="store_true",
                     help="use the library's in-process multi-GPU renderer (rt_multi) even at N=1 (without torchrun)")
@@ -603,6 +615,8 @@ def parse_args(argv=None):
     ap.add_argument("--tile-share", type=int, default=0, metavar="N",
                     help="1-GPU probe of --shard tiles: render only rank 0's stripes of an N-GPU split")
     args = ap.parse_args(argv)
+    if not args.full:
+        args.no_extras = True
     if args.no_extras:
         args.no_counters = args.no_cpu_baseline = True
     return args
@@ -729,8 +743,9 @@ def run(args, backend, cfg=None, json_out=None, golden=None):
     run_steps(args.warmup, warm)
     backend.barrier_sync()
     single = not use_dist and not inlib and not tiles
-    if single and full_frame:
-        ren.clear()                     # the renderer's framebuffer then holds exactly the timed frame
+    dump_dir = getattr(args, "dump_outputs", None)
+    if single and (full_frame or dump_dir):
+        ren.clear()                     # the renderer's framebuffer then holds exactly the timed steps' passes
     timed = {}
     t0 = time.perf_counter()
     my_passes = run_steps(steps, timed)
@@ -741,6 +756,10 @@ def run(args, backend, cfg=None, json_out=None, golden=None):
         timed_fb = frame.fb.detach().to("cpu").numpy().copy()
     elif (inlib or single) and full_frame and rank == 0:
         timed_fb = ren.framebuffer()
+    if dump_dir and rank == 0:
+        # what the timed steps handed their caller: the framebuffer they accumulated and their work counts
+        dump_fb = timed_fb if timed_fb is not None or use_dist else ren.framebuffer()
+        dump_outputs(dump_dir, dump_fb, timed)
 
     # ---- untimed legs (every rank takes part: they contain collectives)
     evrun, counted, frame_s, parity = {}, None, None, None
@@ -898,6 +917,26 @@ def passes_in_flight(inlib):
         cap = min(cap, max(1, int(e)))
     q = os.environ.get("GPU_MAX_HW_QUEUES", "")
     return {"cap": min(cap, int(q) if q.isdigit() and int(q) > 0 else 4), "hw_queues": q or None}
+
+
+DUMP_MAX_BYTES = 48 << 20      # --dump-outputs: a larger framebuffer is written as a fixed, seeded sample of this size
+DUMP_COUNTS = ("passes", "generated_rays", "live_segments")
+
+
+def dump_outputs(dump_dir, fb, stats):
+    """--dump-outputs DIR: DIR/framebuffer.npy, the per-pixel sums the timed steps accumulated (float32, W*H*3, what
+    the renderer's framebuffer read returns after them), and DIR/work_counts.npy, the DUMP_COUNTS entries of the
+    rt_stats they returned, summed over the steps (float64).  The inputs are the scene files and the pass seeds, so
+    two runs with the same arguments write the same arrays."""
+    os.makedirs(dump_dir, exist_ok=True)
+    if fb is not None:
+        fb = np.ascontiguousarray(fb, dtype=np.float32).ravel()
+        if fb.nbytes > DUMP_MAX_BYTES:
+            keep = np.random.default_rng(0).choice(fb.size, DUMP_MAX_BYTES // 4, replace=False)
+            fb = fb[np.sort(keep)]
+        np.save(os.path.join(dump_dir, "framebuffer.npy"), fb)
+    np.save(os.path.join(dump_dir, "work_counts.npy"),
+            np.array([float(stats.get(k, 0)) for k in DUMP_COUNTS], dtype=np.float64))
 
 
 def frame_parity(fb, name, sort, image):

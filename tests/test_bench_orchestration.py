@@ -112,7 +112,7 @@ def _worker(rank, world, port, tmp, steps):
     import bench
     dist.init_process_group("gloo", rank=rank, world_size=world)
     log = []
-    argv = ["--gpus", str(world), "--scene", "cornell_plus", "--warmup", "1"]
+    argv = ["--gpus", str(world), "--scene", "cornell_plus", "--warmup", "1", "--full"]
     if steps:
         argv += ["--steps", str(steps)]
     args = bench.parse_args(argv)
@@ -227,7 +227,8 @@ def test_bench_run_in_library_backend(n, steps, monkeypatch):
     monkeypatch.delenv("WORLD_SIZE", raising=False)
     sys.path.insert(0, REPO)
     import bench
-    args = bench.parse_args(["--gpus", str(n), "--scene", "cornell_plus", "--warmup", "1", "--no-cpu-baseline"] +
+    args = bench.parse_args(["--gpus", str(n), "--scene", "cornell_plus", "--warmup", "1", "--full",
+                             "--no-cpu-baseline"] +
                             (["--steps", str(steps)] if steps else []))
     log = []
     buf = io.StringIO()
@@ -243,6 +244,43 @@ def test_bench_run_in_library_backend(n, steps, monkeypatch):
             sort=True, threads=2)
         assert np.array_equal(res["timed_fb"], ref)
     assert res["my_passes"] == -(-frame_spp // 20)
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path, monkeypatch):
+    """Without --full only the warmup and the timed steps run (no exclusive pass, no parity render, no reruns:
+    one renderer call each), the fields of the moved legs are null, and --dump-outputs DIR writes the timed
+    steps' framebuffer (float32, bit for bit the single-process render) and work counts (float64)."""
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    sys.path.insert(0, REPO)
+    import bench
+    n = 2
+    args = bench.parse_args(["--gpus", str(n), "--scene", "cornell_plus", "--warmup", "1",
+                             "--dump-outputs", str(tmp_path / "out")])
+    log, calls = [], []
+    backend = OracleInLibBackend(log, n)
+    make = backend.renderer
+
+    def counting_renderer(scene, sort, tiles):
+        ren = make(scene, sort, tiles)
+        run = ren.run
+        ren.run = lambda *a, **k: (calls.append(k), run(*a, **k))[1]
+        return ren
+    backend.renderer = counting_renderer
+    buf = io.StringIO()
+    res = bench.run(args, backend, cfg=CFG, json_out=buf)
+    line = json.loads(buf.getvalue().strip())
+    assert log == [] and len(calls) == 2                 # the warmup step and the timed frame
+    assert line["roofline"] is None and line["parity"] is None and line["cpu_baseline"] is None
+    assert line["bit_exact_vs_oracle"] is None and line["render_wall_ms"] is None
+    assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0
+    W, H, spp, bounces = CFG[1:5]
+    ref, _ = O.OracleScene(os.path.join(O.ASSETS, CFG[0]), image=(W, H, spp, bounces)).render(sort=True, threads=2)
+    fb = np.load(tmp_path / "out" / "framebuffer.npy")
+    assert fb.dtype == np.float32 and np.array_equal(fb, ref) and np.array_equal(fb, res["timed_fb"])
+    counts = np.load(tmp_path / "out" / "work_counts.npy")
+    assert counts.dtype == np.float64 and counts.shape == (len(bench.DUMP_COUNTS),)
+    assert counts[bench.DUMP_COUNTS.index("passes")] == 3
+    assert counts[bench.DUMP_COUNTS.index("live_segments")] > 0
 
 
 def test_bench_gpus_argument_is_checked():

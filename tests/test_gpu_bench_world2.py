@@ -82,7 +82,7 @@ def _worker(rank, world, port, tmp, steps, golden):
     backend.world, backend.rank, backend.local = world, rank, 0
     backend.dist, backend.torch, backend.device = StagedDist(dist, torch), torch, torch.device("cuda", 0)
     backend.use_dist = True
-    argv = ["--gpus", str(world), "--scene", "teapot", "--warmup", "1", "--no-cpu-baseline"]
+    argv = ["--gpus", str(world), "--scene", "teapot", "--warmup", "1", "--full", "--no-cpu-baseline"]
     if steps:
         argv += ["--steps", str(steps)]
     buf = io.StringIO()

@@ -80,7 +80,8 @@ def test_bench_gpus2_without_torchrun_loopback(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(RTAMD_LIB=R.TEST_LIB_PATH, RTAMD_MULTI_LOOPBACK="1")
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--scene", "cornell_plus",
-                        "--warmup", "1", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=300)
+                        "--warmup", "1", "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True,
+                       timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     print(json.dumps({k: line[k] for k in ("value", "ms_per_step", "n_gpus", "steps")}))
@@ -95,7 +96,8 @@ def test_bench_inlib_one_gpu_rccl():
     `--gpus N` takes without torchrun); the timed cornell_plus frame equals the oracle's frame hash."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "RTAMD_LIB")}
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--inlib", "--scene", "cornell_plus",
-                        "--warmup", "1", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=300)
+                        "--warmup", "1", "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True,
+                       timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 1 and line["config"]["n_ranks_seen"] == 1 and "rt_multi" in line["config"]["launch"]

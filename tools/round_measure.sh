@@ -46,17 +46,17 @@ if [ "$PART" = A ]; then
   bash tools/pmc.sh ${TAG}_tr tools/pmc_groups/trace.txt > $OUT/pmc_trc.log 2>&1 || { cat $OUT/pmc_trc.log; exit 1; }
   python3 tools/pmc_summary.py ${TAG}_tr > $OUT/pmc_trace_teapot.txt || exit 1
   step bench teapot
-  timeout -k 10 400 python bench.py > $OUT/bench_teapot.json 2> $OUT/bench_teapot.err || { tail $OUT/bench_teapot.err; exit 1; }
+  timeout -k 10 400 python bench.py --full > $OUT/bench_teapot.json 2> $OUT/bench_teapot.err || { tail $OUT/bench_teapot.err; exit 1; }
   cut -c1-300 $OUT/bench_teapot.json
   step bench teapot driver-style
-  timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_teapot_steps20.json 2> $OUT/bench_teapot_steps20.err || { tail $OUT/bench_teapot_steps20.err; exit 1; }
+  timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_teapot_steps20.json 2> $OUT/bench_teapot_steps20.err || { tail $OUT/bench_teapot_steps20.err; exit 1; }
   step rocprof kernel trace
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python3 bench.py --no-cpu-baseline --no-counters > $OUT/prof.log 2>&1 || { tail $OUT/prof.log; exit 1; }
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python3 bench.py --full --no-cpu-baseline --no-counters > $OUT/prof.log 2>&1 || { tail $OUT/prof.log; exit 1; }
   python3 tools/trace_summary.py trace $OUT/prof/run_kernel_trace.csv > $OUT/kernel_trace_summary_teapot.txt || exit 1
 else
   for cfg in cornell_plus spheres lamp teapot:--no-sort lamp:--no-sort cornell; do
     args=$(echo $cfg | tr ':' ' '); name=$(echo $cfg | tr -d ':-'); step bench $args
-    timeout -k 10 400 python bench.py --scene $args > $OUT/bench_$name.json 2> $OUT/bench_$name.err || { tail $OUT/bench_$name.err; exit 1; }
+    timeout -k 10 400 python bench.py --full --scene $args > $OUT/bench_$name.json 2> $OUT/bench_$name.err || { tail $OUT/bench_$name.err; exit 1; }
   done
   step strong-scaling probe
   bash tools/scaling_probe.sh $TAG/scaling > $OUT/scaling_probe.log 2>&1 || { cat $OUT/scaling_probe.log; exit 1; }
