@@ -359,6 +359,132 @@ def trace_rays(scene, rays, device=0, counters=False):
     return t, idx, st.as_dict()
 
 
+def _is_tensor(x):
+    """A torch.Tensor, told without importing torch (a numpy caller never pays for it)."""
+    t = type(x)
+    return t.__module__.split(".")[0] == "torch" and hasattr(x, "data_ptr") and hasattr(x, "is_contiguous")
+
+
+class RayQuery:
+    """rt_query: resident ray queries (scene + BVH in HBM, scratch kept between calls).
+
+    closest(rays) -> (t, index) and occluded(rays, tmax=None) -> mask take rays (n, 6) float32
+    {o.xyz, d.xyz}, either as a numpy array (host path: rt_query_*_host, blocking, numpy results) or as a
+    torch.Tensor on cuda:<device> (float32, shape (n, 6), contiguous; anything else raises ValueError,
+    nothing is copied or converted silently).  For a tensor the results are torch tensors on that device
+    (float32 t, int32 index, bool mask) and the work is enqueued on torch.cuda.current_stream(device)
+    without any synchronisation: they are ready in stream order, like any torch op's."""
+
+    def __init__(self, scene, device=0, counters=False, L=None):
+        self.L = L or lib()
+        self.scene = scene
+        self.device = int(device)
+        self.h = None
+        f = self.L
+        f.rt_query_create.argtypes = [P, P, C.POINTER(P)]
+        f.rt_query_reserve.argtypes = [P, I32]
+        f.rt_query_closest.argtypes = [P, P, I32, P, P, P]
+        f.rt_query_occluded.argtypes = [P, P, P, I32, P, P]
+        f.rt_query_closest_host.argtypes = [P, P, I32, P, P]
+        f.rt_query_occluded_host.argtypes = [P, P, P, I32, P]
+        f.rt_query_stats.argtypes = [P, P]
+        f.rt_query_destroy.argtypes = [P]
+        o = default_opts(True, self.device, counters=counters)
+        h = P()
+        _check(f.rt_query_create(scene.ptr, C.byref(o), C.byref(h)), f)
+        self.h = h
+
+    @staticmethod
+    def check_tensor(x, device, what="rays", shape_tail=(6,)):
+        """Validates a torch tensor argument (float32, shape (n,) + shape_tail, contiguous, on
+        cuda:<device>) with ValueError, before any library call; returns n."""
+        import torch
+        if x.dtype != torch.float32:
+            raise ValueError("%s must be float32, not %s" % (what, x.dtype))
+        if x.dim() != len(shape_tail) + 1 or tuple(x.shape[1:]) != tuple(shape_tail):
+            raise ValueError("%s must have shape (n%s), not %s" % (what, "".join(", %d" % s for s in shape_tail),
+                                                                  tuple(x.shape)))
+        if not x.is_contiguous():
+            raise ValueError("%s must be contiguous" % what)
+        if x.device.type != "cuda" or x.device.index != int(device):
+            raise ValueError("%s must be on cuda:%d, not %s" % (what, int(device), x.device))
+        return int(x.shape[0])
+
+    @staticmethod
+    def _rays_np(rays):
+        a = np.asarray(rays)
+        if a.dtype != np.float32:
+            raise ValueError("rays must be float32, not %s" % a.dtype)
+        if a.ndim != 2 or a.shape[1] != 6:
+            raise ValueError("rays must have shape (n, 6), not %s" % (a.shape,))
+        if not a.flags["C_CONTIGUOUS"]:
+            raise ValueError("rays must be contiguous")
+        return a
+
+    def reserve(self, n):
+        """Size the scratch for n rays now (later calls of up to n rays allocate nothing)."""
+        _check(self.L.rt_query_reserve(self.h, int(n)), self.L)
+
+    def closest(self, rays):
+        """Closest hit: t (1e30 on a miss) and primitive index (-1 on a miss), as trace_rays."""
+        if _is_tensor(rays):
+            import torch
+            n = self.check_tensor(rays, self.device)
+            t = torch.empty(n, dtype=torch.float32, device=rays.device)
+            idx = torch.empty(n, dtype=torch.int32, device=rays.device)
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            _check(self.L.rt_query_closest(self.h, P(rays.data_ptr()), n, P(t.data_ptr()), P(idx.data_ptr()),
+                                           P(stream) if stream else None), self.L)
+            return t, idx
+        a = self._rays_np(rays)
+        n = a.shape[0]
+        t = np.zeros(n, np.float32)
+        idx = np.zeros(n, np.int32)
+        _check(self.L.rt_query_closest_host(self.h, _ptr(a), n, _ptr(t), _ptr(idx)), self.L)
+        return t, idx
+
+    def occluded(self, rays, tmax=None):
+        """Any hit before tmax (per ray; None = 1e30, i.e. anything at all): a bool mask."""
+        if _is_tensor(rays):
+            import torch
+            n = self.check_tensor(rays, self.device)
+            if tmax is not None:
+                if not _is_tensor(tmax):
+                    raise ValueError("tmax must be a torch.Tensor when rays is one")
+                if self.check_tensor(tmax, self.device, "tmax", ()) != n:
+                    raise ValueError("tmax must have one entry per ray")
+            mask = torch.empty(n, dtype=torch.bool, device=rays.device)
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            _check(self.L.rt_query_occluded(self.h, P(rays.data_ptr()), P(tmax.data_ptr()) if tmax is not None else None,
+                                            n, P(mask.data_ptr()), P(stream) if stream else None), self.L)
+            return mask
+        a = self._rays_np(rays)
+        n = a.shape[0]
+        tm = None
+        if tmax is not None:
+            tm = np.asarray(tmax)
+            if tm.dtype != np.float32 or tm.shape != (n,) or not tm.flags["C_CONTIGUOUS"]:
+                raise ValueError("tmax must be a contiguous float32 array of shape (n,)")
+        occ = np.zeros(n, np.uint8)
+        _check(self.L.rt_query_occluded_host(self.h, _ptr(a), _ptr(tm) if tm is not None else None, n, _ptr(occ)),
+               self.L)
+        return occ.view(np.bool_)
+
+    def stats(self):
+        """rt_query_stats: waits for the last call and returns its counters."""
+        st = RtStats()
+        _check(self.L.rt_query_stats(self.h, C.byref(st)), self.L)
+        return st.as_dict()
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.rt_query_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
 class Renderer:
     """Persistent renderer (scene + ray buffers resident in HBM)."""
 

@@ -275,6 +275,52 @@ void rt_multi_destroy(rt_multi *m);
 int rt_trace_rays(const rt_scene *scene, const rt_opts *opts, const float *rays, int32_t n,
                   float *t_out, int32_t *index_out, rt_stats *stats);
 
+/* Resident ray queries: the scene and BVH stay in HBM (a scene-only renderer: no pass contexts, so the
+ * object costs the scene plus its scratch) and device pointers go in and out on the caller's stream.
+ * The presence of these symbols is the feature probe; RT_ABI_VERSION, rt_opts and rt_stats are unchanged.
+ * No reference counterpart as an interface (the reference traced only its own render's rays); what each
+ * call computes restates the reference's traversal:
+ *   rt_query_closest   the sphere loop (scene.cu:338-372) then bvh_closest_hit_distance (scene.cu:134-241)
+ *                      with `closest` starting at 1e30 -- rt_trace_rays' semantics exactly (t = 1e30 and
+ *                      index = -1 on a miss, NaN behaviour included), through the render's trace kernel.
+ *   rt_query_occluded  the same sphere loop and traversal with `closest` held at the ray's bound B and
+ *                      never updated: 1 iff some primitive is accepted.  B = tmax[i] where tmax[i] <= 1e30,
+ *                      otherwise (larger, +inf, NaN, or d_tmax NULL) 1e30.  That is: every sphere tested
+ *                      with closest = B (scene.cu:340-371); the root entered iff !(0 >= B); in a leaf every
+ *                      triangle tested with closest = B (scene.cu:160-195); at an internal node a child
+ *                      entered iff ray_aabb_intersection(child, tmax = B) (scene.cu:109-132) holds and
+ *                      !(entry >= B) (scene.cu:147-152).  t < 0.005 rejects as everywhere.  Because B never
+ *                      shrinks, which nodes are entered does not depend on the visit order, so the kernel
+ *                      visits the near child first and stops at the first accepted primitive; the answer is
+ *                      the reference-order answer bit for bit.  Against the closest hit (t_c, index):
+ *                      occluded implies t_c < B, and for B = 1e30 occluded <=> index >= 0; t_c < B does NOT
+ *                      imply occluded when B lies just above t_c (a box's float entry distance can exceed
+ *                      the triangle's float t, and the fixed bound then prunes the box).
+ * rays = n x {o.x o.y o.z d.x d.y d.z} floats, contiguous, d unit length.  The device-pointer calls take
+ * pointers on q's device and enqueue on hip_stream (a hipStream_t, passed to HIP as given: NULL is HIP's
+ * default stream, which is also torch's default); once the scratch holds n rays (rt_query_reserve, or an
+ * earlier call of at least that size; it grows geometrically) they allocate nothing and never wait on the
+ * host.  Each call records an event the next call's stream waits for, so alternating streams is safe; the
+ * caller keeps its own buffers alive and unmodified until the call's work on hip_stream has finished.
+ * The _host calls take host pointers and block.  n == 0 returns RT_OK and touches no pointer; a null
+ * object, n < 0 or a null pointer with n > 0 (d_tmax / tmax excepted) return RT_E_INVALID before any HIP
+ * call.  Uses opts->device and opts->collect_counters.  One thread at a time per object; distinct objects
+ * may run concurrently.
+ * rt_query_stats waits for the last call and returns its counters: live_segments = n, hits = the hit or
+ * occluded count, misses = the rest, hits_sphere (closest only); with collect_counters also Pn/Iv/Tt and
+ * sphere_tests -- the oracle's for closest; for occluded exact on unoccluded rays and order-dependent on
+ * occluded ones (the sphere loop stops at the first accepted sphere). */
+typedef struct rt_query rt_query;
+int rt_query_create(const rt_scene *scene, const rt_opts *opts, rt_query **out);
+int rt_query_reserve(rt_query *q, int32_t n);   /* size the scratch for n rays now */
+int rt_query_closest(rt_query *q, const float *d_rays, int32_t n, float *d_t, int32_t *d_index, void *hip_stream);
+int rt_query_occluded(rt_query *q, const float *d_rays, const float *d_tmax /* NULL = 1e30 */, int32_t n,
+                      uint8_t *d_occluded /* 0 or 1 */, void *hip_stream);
+int rt_query_closest_host(rt_query *q, const float *rays, int32_t n, float *t, int32_t *index);
+int rt_query_occluded_host(rt_query *q, const float *rays, const float *tmax, int32_t n, uint8_t *occluded);
+int rt_query_stats(rt_query *q, rt_stats *stats);
+void rt_query_destroy(rt_query *q);
+
 /* Replaces the bloom block of main (raytracing.cu:356-393, kernels :21-74): high-pass
  * (luminance > threshold), clamped box blur of `radius` horizontally then vertically,
  * add back.  fb is a host W*H*3 buffer, updated in place. */
