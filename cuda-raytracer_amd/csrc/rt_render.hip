@@ -16,6 +16,8 @@
 //   * accumulation is an ordered per-pixel sum (deterministic; no float atomics).
 #include "rt_abi.h"
 #include "rt_device.h"
+#include "bvh_refit.h"
+#include "bvh_refit_math.h"
 
 #include <algorithm>
 #include <chrono>
@@ -1808,6 +1810,7 @@ struct rt_renderer {
     DevBuf<float4> spheres, tris, mats, nodes;
     DevBuf<uint16_t> mat_idx;
     DevBuf<int2> big;
+    std::vector<int> node_rec;        // node -> child-pair record (-1: leaf), kept for a scene-only renderer (refit)
     DevBuf<float> env, fb;
     DevBuf<Counters> ctr;
     DevBuf<unsigned long long> tspans;   // per run: [pass][bounce] trace-launch wall-clock spans (event timing on)
@@ -1975,6 +1978,7 @@ struct rt_renderer {
         }
         ds.root_ref = nn > 0 ? ref_of(0) : (kLeaf | 0u);
         if (big_h.empty()) big_h.push_back(make_int2(0, 0));
+        if (!passes) node_rec = rec;
         if ((rc = spheres.upload(sc->spheres, sc->sphere_count, s0))) return rc;
         // one float4 of slack: traversal reads 64 B at a triangle record (48 B) like at a node
         if ((rc = tris.upload(sc->triangles, (size_t)sc->triangle_count * 3, s0, 1))) return rc;
@@ -2877,8 +2881,9 @@ struct rt_query {
     DevBuf<uint8_t> s_occ;
     hipEvent_t last = nullptr;
     bool pending = false;             // `last` has been recorded
-    int last_kind = 0;                // 0 none, 1 closest, 2 occluded
+    int last_kind = 0;                // 0 none (or an update), 1 closest, 2 occluded
     int32_t last_n = 0;
+    rtamd::RefitPlan plan;            // rt_query_update_triangles: level tables, built in init
 
     ~rt_query() {
         (void)hipSetDevice(r.device);
@@ -2899,6 +2904,7 @@ struct rt_query {
         blocks = std::max(1, r.cus * std::max({1, per_cu_c, per_cu_a}));
         HIPCHK(hipEventCreateWithFlags(&last, hipEventDisableTiming));
         if ((rc = words.alloc((size_t)(1 + kQueues) * kQueueStride))) return rc;
+        if ((rc = plan.build(sc, r.node_rec, r.stream()))) return rc;
         // trace_kernel: 2 words (ref, distance) for each of kStackMax - kStackLds entries per lane; the
         // any-hit kernel's kStackMax - kAnyStackLds one-word entries fit in the same buffer
         return overflow.alloc((size_t)blocks * kBlock * 2 * (kStackMax - kStackLds));
@@ -2996,12 +3002,71 @@ struct rt_query {
         HIPCHK(hipStreamSynchronize(s));
         return RT_OK;
     }
+    // New vertices under the frozen topology.  An update overwrites what a query reads, so
+    // it joins the `last` chain like a query: queries enqueued later, on any stream, see the new geometry.
+    int update(const float *d_vertices, hipStream_t s) {
+        HIPCHK(hipSetDevice(r.device));
+        if (pending) HIPCHK(hipStreamWaitEvent(s, last, 0));
+        int rc = plan.enqueue(d_vertices, r.tris.p, r.nodes.p, r.big.p, s);
+        if (rc) return rc;
+        return end(0, 0, s);
+    }
+    int update_host(const float *vertices) {
+        HIPCHK(hipSetDevice(r.device));
+        const size_t count = (size_t)plan.triangle_count * 9;
+        if (!plan.d_stage) HIPCHK(hipMalloc(reinterpret_cast<void **>(&plan.d_stage), count * sizeof(float)));
+        hipStream_t s = r.stream();
+        HIPCHK(hipMemcpyAsync(plan.d_stage, vertices, count * sizeof(float), hipMemcpyHostToDevice, s));
+        int rc = update(plan.d_stage, s);
+        if (rc) return rc;
+        HIPCHK(hipStreamSynchronize(s));
+        return RT_OK;
+    }
+    // The device's current triangles and the node array in the scene's numbering (inspection, tests).
+    int read_geometry(rt_triangle *tris_out, rt_bvh_node *bvh_out) {
+        HIPCHK(hipSetDevice(r.device));
+        int rc = wait_last();
+        if (rc) return rc;
+        if (tris_out && plan.triangle_count)
+            HIPCHK(hipMemcpy(tris_out, r.tris.p, (size_t)plan.triangle_count * sizeof(rt_triangle), hipMemcpyDeviceToHost));
+        if (!bvh_out) return RT_OK;
+        using rtamd::refit::Box;
+        std::copy(plan.bvh.begin(), plan.bvh.end(), bvh_out);
+        if (plan.root_leaf) {
+            float4 box[2];
+            HIPCHK(hipMemcpy(box, plan.d_root_box, sizeof(box), hipMemcpyDeviceToHost));
+            bvh_out[0].min_bound = {box[0].x, box[0].y, box[0].z};
+            bvh_out[0].max_bound = {box[1].x, box[1].y, box[1].z};
+            return RT_OK;
+        }
+        std::vector<float4> rec_h(plan.rec_node.size() * 4);
+        HIPCHK(hipMemcpy(rec_h.data(), r.nodes.p, rec_h.size() * sizeof(float4), hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < plan.rec_node.size(); k++) {
+            const int i = plan.rec_node[k];
+            if (i < 0) continue;
+            const float4 *q = &rec_h[k * 4];
+            rt_bvh_node &l = bvh_out[plan.bvh[i].child1], &rr = bvh_out[plan.bvh[i].child2];
+            l.min_bound = {q[0].x, q[0].z, q[1].x};
+            l.max_bound = {q[1].z, q[2].x, q[2].z};
+            rr.min_bound = {q[0].y, q[0].w, q[1].y};
+            rr.max_bound = {q[1].w, q[2].y, q[2].w};
+            if (i == 0) {                   // the root's own box: the merge of its record
+                Box b = rtamd::refit::empty_box();
+                rtamd::refit::grow(b, Box{l.min_bound, l.max_bound});
+                rtamd::refit::grow(b, Box{rr.min_bound, rr.max_bound});
+                bvh_out[0].min_bound = b.lo;
+                bvh_out[0].max_bound = b.hi;
+            }
+        }
+        return RT_OK;
+    }
     int stats(rt_stats *st) {
         std::memset(st, 0, sizeof(*st));
         if (!pending) return RT_OK;
         HIPCHK(hipSetDevice(r.device));
         int rc = wait_last();
         if (rc) return rc;
+        if (last_kind == 0) return RT_OK;   // an update since the last query: nothing was traced
         std::vector<Counters> slots(kCtrSlots);
         HIPCHK(hipMemcpy(slots.data(), r.ctr.p, sizeof(Counters) * kCtrSlots, hipMemcpyDeviceToHost));
         for (const Counters &x : slots) {
@@ -3366,6 +3431,33 @@ int rt_query_occluded_host(rt_query *q, const float *rays, const float *tmax, in
 int rt_query_stats(rt_query *q, rt_stats *stats) {
     if (!q || !stats) return rtamd::fail(RT_E_INVALID, "rt_query_stats: null argument");
     return q->stats(stats);
+}
+
+static_assert(rtamd::kRefLeaf == kLeaf && rtamd::kRefBigLeaf == kBigLeaf, "bvh_refit.hip reads the records' leaf refs");
+
+int rt_query_update_triangles(rt_query *q, const float *d_vertices, int32_t triangle_count, void *hip_stream) {
+    if (!q) return rtamd::fail(RT_E_INVALID, "rt_query_update_triangles: null query object");
+    if (triangle_count != q->plan.triangle_count)
+        return rtamd::fail(RT_E_INVALID, "rt_query_update_triangles: triangle_count " + std::to_string(triangle_count) +
+                                             " is not the scene's " + std::to_string(q->plan.triangle_count));
+    if (triangle_count == 0) return RT_OK;
+    if (!d_vertices) return rtamd::fail(RT_E_INVALID, "rt_query_update_triangles: null pointer");
+    return q->update(d_vertices, static_cast<hipStream_t>(hip_stream));
+}
+
+int rt_query_update_triangles_host(rt_query *q, const float *vertices, int32_t triangle_count) {
+    if (!q) return rtamd::fail(RT_E_INVALID, "rt_query_update_triangles_host: null query object");
+    if (triangle_count != q->plan.triangle_count)
+        return rtamd::fail(RT_E_INVALID, "rt_query_update_triangles_host: triangle_count " + std::to_string(triangle_count) +
+                                             " is not the scene's " + std::to_string(q->plan.triangle_count));
+    if (triangle_count == 0) return RT_OK;
+    if (!vertices) return rtamd::fail(RT_E_INVALID, "rt_query_update_triangles_host: null pointer");
+    return q->update_host(vertices);
+}
+
+int rt_query_read_geometry(rt_query *q, rt_triangle *triangles_out, rt_bvh_node *bvh_out) {
+    if (!q) return rtamd::fail(RT_E_INVALID, "rt_query_read_geometry: null query object");
+    return q->read_geometry(triangles_out, bvh_out);
 }
 
 void rt_query_destroy(rt_query *q) { delete q; }

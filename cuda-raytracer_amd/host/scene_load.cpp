@@ -353,17 +353,6 @@ int load_pfm(const std::string &path, std::vector<rt_vec3> &env, int &w, int &h)
 }  // namespace
 }  // namespace rtamd
 
-struct rt_scene_host {
-    rt_scene view{};
-    std::vector<rt_sphere> spheres;
-    std::vector<rt_triangle> triangles;
-    std::vector<uint16_t> material_indices;
-    std::vector<rt_material> materials;
-    std::vector<rt_bvh_node> bvh;
-    std::vector<rt_vec3> env;
-    double bvh_ms = 0;
-};
-
 using namespace rtamd;
 
 extern "C" {

@@ -221,6 +221,22 @@ class Scene:
     def bvh_ms(self):
         return lib().rt_scene_bvh_ms(self.h)
 
+    def vertices(self):
+        """The triangles' vertices, (n, 9) float32 {a.xyz, b.xyz, c.xyz} in the scene's triangle order,
+        reconstructed from the records as p1, p1 + p2p1, p1 + p3p1: not necessarily the file's floats
+        (b - a + a need not be b).  This is what a caller deforms and hands to refit / RayQuery.update."""
+        t = self.arrays()["triangles"]
+        return np.ascontiguousarray(np.hstack([t[:, 0:3], t[:, 0:3] + t[:, 3:6], t[:, 0:3] + t[:, 6:9]]), np.float32)
+
+    def refit(self, vertices):
+        """rt_scene_refit: new vertices (numpy (n, 9) float32, contiguous, the scene's triangle order)
+        under the frozen BVH topology; triangles, node bounds and the reorder-key bounds are rewritten in
+        place.  Objects created from the scene earlier keep their own device copies."""
+        a = _vertices_np(vertices)
+        f = lib().rt_scene_refit
+        f.argtypes = [P, P, I32]
+        _check(f(self.h, _ptr(a), a.shape[0]))
+
     def arrays(self):
         v = self.view
 
@@ -244,6 +260,20 @@ class Scene:
                     bvh=arr(v.bvh, v.bvh_node_count, 8),
                     env=arr(v.environment_map, v.environment_map_width * v.environment_map_height, 3),
                     camera=cam)
+
+
+def _vertices_np(vertices):
+    """Validates refit vertices given as numpy: (n, 9) float32, contiguous; nothing is converted."""
+    a = vertices
+    if not isinstance(a, np.ndarray):
+        raise ValueError("vertices must be a numpy array, not %s" % type(a).__name__)
+    if a.dtype != np.float32:
+        raise ValueError("vertices must be float32, not %s" % a.dtype)
+    if a.ndim != 2 or a.shape[1] != 9:
+        raise ValueError("vertices must have shape (n, 9), not %s" % (a.shape,))
+    if not a.flags["C_CONTIGUOUS"]:
+        raise ValueError("vertices must be contiguous")
+    return a
 
 
 def default_opts(sort=True, device=0, pass_begin=0, pass_count=-1, pass_stride=1, counters=False,
@@ -469,6 +499,35 @@ class RayQuery:
         _check(self.L.rt_query_occluded_host(self.h, _ptr(a), _ptr(tm) if tm is not None else None, n, _ptr(occ)),
                self.L)
         return occ.view(np.bool_)
+
+    def update(self, vertices):
+        """rt_query_update_triangles: new vertices (n, 9) float32 {a.xyz, b.xyz, c.xyz} in the scene's
+        triangle order, under the frozen BVH topology (a refit of the resident records).  A numpy array
+        goes through the _host call (staged, blocking); a torch.Tensor on cuda:<device> is read in place
+        and the work is enqueued on torch.cuda.current_stream(device) without any synchronisation.  Queries
+        enqueued afterwards, on any stream, see the new geometry.  Anything else raises ValueError."""
+        f = self.L
+        if _is_tensor(vertices):
+            import torch
+            n = self.check_tensor(vertices, self.device, "vertices", shape_tail=(9,))
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            f.rt_query_update_triangles.argtypes = [P, P, I32, P]
+            _check(f.rt_query_update_triangles(self.h, P(vertices.data_ptr()), n, P(stream) if stream else None), f)
+            return
+        a = _vertices_np(vertices)
+        f.rt_query_update_triangles_host.argtypes = [P, P, I32]
+        _check(f.rt_query_update_triangles_host(self.h, _ptr(a), a.shape[0]), f)
+
+    def geometry(self):
+        """rt_query_read_geometry: waits, then returns the device's current (triangles (n, 12), bvh (m, 8))
+        as float32 arrays laid out like Scene.arrays()' (the bvh's last two columns are the int32 children)."""
+        v = self.scene.view
+        tri = np.zeros((v.triangle_count, 12), np.float32)
+        bvh = np.zeros((v.bvh_node_count, 8), np.float32)
+        f = self.L.rt_query_read_geometry
+        f.argtypes = [P, P, P]
+        _check(f(self.h, _ptr(tri), _ptr(bvh)), self.L)
+        return tri, bvh
 
     def stats(self):
         """rt_query_stats: waits for the last call and returns its counters."""

@@ -321,6 +321,44 @@ int rt_query_occluded_host(rt_query *q, const float *rays, const float *tmax, in
 int rt_query_stats(rt_query *q, rt_stats *stats);
 void rt_query_destroy(rt_query *q);
 
+/* Dynamic geometry: new triangle vertices under the frozen BVH topology (a refit).  The
+ * presence of these symbols is the feature probe; RT_ABI_VERSION and every struct are unchanged.  No
+ * reference counterpart (the reference's scenes are static).
+ * vertices = triangle_count x 9 floats, {a.xyz, b.xyz, c.xyz} per triangle IN THE SCENE'S TRIANGLE ORDER
+ * (rt_scene.triangles, i.e. after the builder's permutation); triangle_count must equal the scene's.
+ *   triangle record i:  p1 = a, p2p1 = b - a, p3p1 = c - a, normal = normalise(cross(p3p1, p2p1)) with the
+ *                       loader's normalise (scale(1 / sqrtf(dot), v)), no contraction.
+ *   bounds:             from the absolute vertices, never from p1 + edge, with the loader's min/max
+ *                       ((b < a) ? b : a, which keeps the earlier operand of a tie; never the hardware min,
+ *                       which orders -0 below +0).  box(tri) = grow over a, b, c from (1e30, -1e30); a leaf
+ *                       over [child2, child1) = grow over box(tri) in index order from (1e30, -1e30); an
+ *                       internal node = grow(grow(init, box(child1)), box(child2)).  "Earliest of the
+ *                       smallest" is associative, so this hierarchical fold is the builder's linear fold
+ *                       over the node's range in the scene's triangle order.
+ *   untouched:          child indices, leaf ranges, triangle order, material indices, spheres.
+ * rt_scene_refit rewrites a loaded scene's triangles and node bounds in place (the rt_scene view stays
+ * valid) and recomputes min_coord / inv_dimensions as the loader does; a render or query created from the
+ * scene afterwards sees the new geometry, objects created earlier keep their own device copies.
+ * rt_query_update_triangles does the same to q's resident records, bit-identical to rt_scene_refit, from
+ * a device pointer on q's device: enqueued on hip_stream (one triangle kernel, then one launch per BVH
+ * level from the deepest up, the levels that fit one workgroup chained in a single-workgroup launch; a
+ * scene whose root is a leaf has no node records and gets the triangle kernel plus a one-workgroup fold of
+ * the root's box, which only rt_query_read_geometry reads).  It allocates nothing and never waits on the
+ * host.  It joins the queries' event chain: hip_stream first waits for the last call on q, and queries
+ * enqueued later (on any stream) see the new geometry, earlier ones the old; d_vertices is read in stream
+ * order and must stay alive and unmodified until then.  The _host variant stages host vertices (its
+ * staging buffer is allocated by the first such call) and blocks.  After an update, with no query since,
+ * rt_query_stats returns zeros.
+ * rt_query_read_geometry waits for the last call, then copies out the device's current triangle records
+ * (triangle_count) and/or the node array in the scene's numbering (bvh_node_count; the root's own box is
+ * the merge of its two children's); either pointer may be NULL.  For inspection and tests.
+ * Errors (RT_E_INVALID with a message, before any launch): a null object or pointer, triangle_count other
+ * than the scene's.  triangle_count 0 on a scene without triangles is a no-op. */
+int rt_scene_refit(rt_scene_host *scene, const float *vertices, int32_t triangle_count);
+int rt_query_update_triangles(rt_query *q, const float *d_vertices, int32_t triangle_count, void *hip_stream);
+int rt_query_update_triangles_host(rt_query *q, const float *vertices, int32_t triangle_count);
+int rt_query_read_geometry(rt_query *q, rt_triangle *triangles_out, rt_bvh_node *bvh_out);
+
 /* Replaces the bloom block of main (raytracing.cu:356-393, kernels :21-74): high-pass
  * (luminance > threshold), clamped box blur of `radius` horizontally then vertically,
  * add back.  fb is a host W*H*3 buffer, updated in place. */
