@@ -1,4 +1,4 @@
-// bvh_refit.h — device refit of a resident scene (csrc/bvh_refit.hip), used by rt_query (rt_render.hip).
+// bvh_refit.h — device refit of a resident scene (csrc/bvh_refit.hip), used by rt_query (rt_query.hip).
 #pragma once
 #include "rt_abi.h"
 
@@ -9,10 +9,7 @@
 
 namespace rtamd {
 
-// Leaf refs of the child-pair records, as rt_render.hip lays them out (kLeaf, kBigLeaf there).
-constexpr uint32_t kRefLeaf = 0x80000000u, kRefBigLeaf = 0x40000000u;
-
-// Built once per object, on the host, from the record numbering the renderer's init computes: the
+// Built once per object, on the host, from the record numbering of bvh_records.h: the
 // records sorted by depth (deepest level first), the level offsets, the launch list and the record ->
 // node map.  Everything an update needs on the device is allocated here, so updates allocate nothing.
 struct RefitPlan {
@@ -32,7 +29,7 @@ struct RefitPlan {
     float *d_stage = nullptr;               // vertices of the host-pointer update (first such call)
 
     ~RefitPlan();
-    // node_rec: node -> its child-pair record (-1 for leaves), rt_renderer::init's numbering
+    // node_rec: node -> its child-pair record (-1 for leaves), records::build's numbering
     int build(const rt_scene *sc, const std::vector<int> &node_rec, hipStream_t s);
     // Enqueues the triangle kernel and the level launches on s.  tris: the 48-B records (+ slack),
     // nodes: the 64-B child-pair records, big: the {begin, end} table of big leaves.

@@ -12,7 +12,7 @@
 // one CU, whose waves share its L1), so a 30-level chain is one launch.
 #include "bvh_refit.h"
 #include "bvh_refit_math.h"
-#include "rt_host.h"
+#include "rt_common.h"
 
 #include <algorithm>
 #include <string>
@@ -20,17 +20,6 @@
 
 namespace rtamd {
 namespace {
-
-constexpr int kBlock = 256;
-
-int hip_fail(hipError_t e, const char *what) {
-    return fail(e == hipErrorOutOfMemory ? RT_E_OOM : RT_E_HIP, std::string("Error ") + what + " " + hipGetErrorString(e));
-}
-#define HIPCHK(call)                                          \
-    do {                                                      \
-        const hipError_t e_ = (call);                         \
-        if (e_ != hipSuccess) return hip_fail(e_, #call);     \
-    } while (0)
 
 using refit::Box;
 
@@ -56,9 +45,9 @@ __global__ __launch_bounds__(kBlock) void refit_triangles_kernel(const float *__
 // two boxes stored in that child's record (child1's, then child2's).
 __device__ __forceinline__ Box slot_box(uint32_t ref, const float4 *nodes, const float *v, const int2 *big) {
     Box b = refit::empty_box();
-    if (ref & kRefLeaf) {
+    if (ref & kLeaf) {
         int ti, te;
-        if (ref & kRefBigLeaf) {
+        if (ref & kBigLeaf) {
             const int2 be = big[ref & 0x3FFFFFFFu];
             ti = be.x; te = be.y;
         } else {
@@ -80,7 +69,7 @@ __device__ __forceinline__ void refit_record(uint32_t rec, float4 *nodes, const 
     const float4 refs = q[3];
     const Box l = slot_box(__float_as_uint(refs.x), nodes, v, big);
     const Box r = slot_box(__float_as_uint(refs.y), nodes, v, big);
-    // the two children's bounds interleaved per plane (rt_renderer::init)
+    // the two children's bounds interleaved per plane (bvh_records.h)
     q[0] = make_float4(l.lo.x, r.lo.x, l.lo.y, r.lo.y);
     q[1] = make_float4(l.lo.z, r.lo.z, l.hi.x, r.hi.x);
     q[2] = make_float4(l.hi.y, r.hi.y, l.hi.z, r.hi.z);
@@ -152,7 +141,7 @@ int RefitPlan::build(const rt_scene *sc, const std::vector<int> &node_rec, hipSt
     std::vector<int> depth((size_t)nrec, -1);
     int max_depth = -1;
     if (!root_leaf) {
-        // the renderer's init has walked the tree (it is one, at most kStackMax levels, indices in range)
+        // records::build has walked the tree (it is one, at most kStackMax levels, indices in range)
         std::vector<std::pair<int, int>> todo{{0, 0}};
         while (!todo.empty()) {
             const int i = todo.back().first, d = todo.back().second;

@@ -14,10 +14,12 @@
 //     SURVEY §8a rows K/L): tile histograms, per-bucket scan, and a scatter that ranks with
 //     seven 64-lane __ballot()s per round;
 //   * accumulation is an ordered per-pixel sum (deterministic; no float atomics).
-#include "rt_abi.h"
-#include "rt_device.h"
-#include "bvh_refit.h"
-#include "bvh_refit_math.h"
+// This file holds the render's kernels, the renderer (rt_renderer: option parsing, pass contexts, the pass
+// schedule) and its C ABI.  Beside it: rt_common.h (constants, DevScene, the traversal building blocks and HIP
+// helpers shared with the other .hip files), scene_dev.hip (SceneDev, the resident scene a renderer owns;
+// the node records come from host/bvh_records.cpp), rt_query.hip (the ray-query kernels and rt_query_*, which
+// launch this file's trace_kernel through launch_trace_closest), bvh_refit.hip, rt_multi.hip.
+#include "rt_common.h"
 
 #include <algorithm>
 #include <chrono>
@@ -32,28 +34,13 @@
 
 #pragma clang fp contract(off)
 
-namespace rtamd {
-int fail(int code, const std::string &msg);
-}
 int rtamd_render_multi(const rt_scene *scene, const rt_opts *opts, float *fb_out, rt_stats *stats);   // rt_multi.hip
 
-using namespace rtd;
+using namespace rtamd;
 
 namespace {
 
-// Tuning knobs (compile-time; -D overrides are for A/B experiments only).
-#ifndef RT_STACK_LDS
-#define RT_STACK_LDS 8
-#endif
-#ifndef RT_REFILL
-#define RT_REFILL 24                  // A/B at 16 passes in flight: 24 beats 16 by ~1 % (teapot, lamp); 8 is worse
-#endif
-#ifndef RT_REFILL_FIRST
-#define RT_REFILL_FIRST 64
-#endif
-#ifndef RT_CHUNK_MAX
-#define RT_CHUNK_MAX 128
-#endif
+// Tuning knobs (compile-time; -D overrides are for A/B experiments only; the traversal's are in rt_common.h).
 #ifndef RT_INFLIGHT
 #define RT_INFLIGHT 20                // with 24 HW queues: +1.5 % teapot, +3.4 % lamp over 16 (24 in flight: worse)
 #endif
@@ -63,17 +50,8 @@ namespace {
 #ifndef RT_TRACE_OCC_MIN
 #define RT_TRACE_OCC_MIN 15
 #endif
-#ifndef RT_QUEUES
-#define RT_QUEUES 8
-#endif
-constexpr int kBlock = 256;           // threads per workgroup (4 waves)
-constexpr int kStackLds = RT_STACK_LDS; // stack entries per lane kept in LDS (deeper: global)
-constexpr int kStackMax = 32;         // >= MAX_BVH_DEPTH + 1 (scene.cu:10, :138)
 #ifndef RT_SORT_ITEMS
 #define RT_SORT_ITEMS 16
-#endif
-#ifndef RT_CHUNK_MIN
-#define RT_CHUNK_MIN 64
 #endif
 #ifndef RT_SHADE_BPC
 #define RT_SHADE_BPC 8
@@ -105,12 +83,6 @@ inline int tile_stride(int64_t n_max) {
     return (int)std::max<int64_t>(kTileTarget, (n_max + kSortTile - 1) / kSortTile);
 }
 constexpr int kBuckets = 65;
-constexpr int kCtrSlots = 64;       // striped copies of the work counters
-constexpr int kChunkMax = RT_CHUNK_MAX; // slots a wave takes from the trace queue per atomic...
-constexpr int kChunkMin = RT_CHUNK_MIN; // ...shrunk so that every wave gets ~4 chunks when few rays live
-constexpr int kRefill = RT_REFILL;   // refill a wave once this many lanes are idle
-constexpr int kRefillFirst = RT_REFILL_FIRST;   // same at bounce 0: a whole wave of consecutive primary rays
-                                                // (~3 pixels) starts together and stays in lockstep
 constexpr int kInflight = RT_INFLIGHT; // passes in flight (one stream and buffer set each)
 constexpr int kStaggerUs = 4000;       // staggered start of the first passes in flight (rt_renderer::run):
 constexpr int kStaggerGroup = 4;       // the first kStaggerGroup together, then one every kStaggerUs
@@ -121,8 +93,6 @@ constexpr int kStaggerShortUs = 2000;  // the same for runs shorter than the pas
 // 100 % (20 in flight: 15 %; A/B at 20 in flight: 40 % 7.51, 30 % 7.41, 20 % 7.37, 15 % 7.33,
 // 10 % 7.35 ms/pass; lamp and the 13-pass share also best at 15 %).
 constexpr int kTraceOccPct = RT_TRACE_OCC;
-constexpr int kQueues = RT_QUEUES;   // trace queue shards (one per XCD group of workgroups)
-constexpr int kQueueStride = 64;     // words between shards (256 B: one shard per cache line)
 constexpr uint32_t kDead = 64;        // bucket of a terminated ray (key 0xFFFFFFFF)
 constexpr uint32_t kAccFlag = 0x80000000u;   // in a ray id (rid): acc[ray] holds the ray's radiance so far
 // Per-launch span words (rt_renderer_set_event_timing): 8 start slots then 8 end slots, one per XCD
@@ -131,23 +101,6 @@ constexpr uint32_t kAccFlag = 0x80000000u;   // in a ray id (rid): acc[ray] hold
 // 0.82 vs the profiler's 0.66 ms per exclusive teapot launch).
 constexpr int kSpanSlots = 8;
 constexpr int kSpanWords = 2 * kSpanSlots;
-constexpr uint32_t kLeaf = 0x80000000u, kBigLeaf = 0x40000000u;
-
-struct DevScene {
-    const float4 *spheres;            // center.xyz, radius
-    const float4 *tris;               // 3 x float4: p1.xyz e1.x | e1.yz e2.xy | e2.z n.xyz
-    const uint16_t *mat_idx;
-    const float4 *mats;               // 3 x float4: diffuse,metal | specular,rough | emit,ior
-    const float4 *nodes;              // 4 x float4 per internal node (child-pair record)
-    const int2 *big_leaves;           // {begin, end} for leaves that do not fit a ref
-    const float *env;                 // env_h * env_w * 3
-    int sphere_count, env_w, env_h, width, height;
-    uint32_t root_ref;
-    V3 cam, tl, sr, su, min_coord, inv_dim;
-    float inv_w, inv_h;
-};
-
-
 #ifdef RT_PROFILE
 // Wave-level traversal profile (debug builds only): see tools/variants.sh + RT_PROFILE=1.
 __device__ unsigned long long g_prof[2][14];   // [bounce 0, later bounces]
@@ -155,23 +108,6 @@ __device__ unsigned long long g_prof[2][14];   // [bounce 0, later bounces]
 #else
 #define PROF(i, v) ((void)0)
 #endif
-
-struct Counters {                     // device-side work counters (u64, one atomic per wave)
-    unsigned long long live, pn, iv, tt, st, hits, misses, hits_sphere;
-};
-
-__device__ __forceinline__ unsigned long long wave_sum(unsigned v) {
-    unsigned long long s = v;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-    return s;
-}
-
-__device__ __forceinline__ uint32_t rank_below(unsigned long long mask) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
-
-__device__ __forceinline__ uint32_t lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 
 // ---------------------------------------------------------------- ray generation
 // generate_initial_rays (scene.cu:78-105, raytracing.cu:76-81), evaluated where a bounce-0 ray
@@ -242,87 +178,19 @@ __device__ __forceinline__ V3 primary_dir(const DevScene &S, int i, const PassAr
 }
 
 // ---------------------------------------------------------------- traversal
-typedef float f2 __attribute__((ext_vector_type(2)));
-
-
-// Both children's slab tests (ray_aabb_intersection, scene.cu:109-132) on the interleaved node
-// record {lx0 lx1 ly0 ly1} {lz0 lz1 hx0 hx1} {hy0 hy1 hz0 hz1}: the plane distances of the two
-// boxes share packed-fp32 ops.  The reference folds the three axes in sequence,
-//   tmin = fminf(fmaxf(t1, tmin), fmaxf(t2, tmin)),  tmax = fmaxf(fminf(t1, tmax), fminf(t2, tmax)),
-// which for NaN-free t1/t2 is exactly tmin = max(min_x, min_y, min_z, 0) and
-// tmax = min(max_x, max_y, max_z, closest) (min/max do not round; zero signs never reach a
-// comparison outcome).  t is NaN only for 0 * inf, so the caller uses this form only when all of
-// 1/d is finite and otherwise the literal per-axis fold (slab()).
-__device__ __forceinline__ void slab_pair(float4 a, float4 b, float4 c, V3 o, float ix, float iy, float iz,
-                                          float closest, bool &h0, bool &h1, float &t0, float &t1) {
-    const f2 ox = {o.x, o.x}, oy = {o.y, o.y}, oz = {o.z, o.z};
-    const f2 vx = {ix, ix}, vy = {iy, iy}, vz = {iz, iz};
-    const f2 lx = {a.x, a.y}, ly = {a.z, a.w}, lz = {b.x, b.y};
-    const f2 hx = {b.z, b.w}, hy = {c.x, c.y}, hz = {c.z, c.w};
-    const f2 x1 = (lx - ox) * vx, x2 = (hx - ox) * vx;
-    const f2 y1 = (ly - oy) * vy, y2 = (hy - oy) * vy;
-    const f2 z1 = (lz - oz) * vz, z2 = (hz - oz) * vz;
-    const float n0 = fmaxf(fmaxf(fminf(x1.x, x2.x), fminf(y1.x, y2.x)), fmaxf(fminf(z1.x, z2.x), 0.0f));
-    const float f0 = fminf(fminf(fmaxf(x1.x, x2.x), fmaxf(y1.x, y2.x)), fminf(fmaxf(z1.x, z2.x), closest));
-    const float n1 = fmaxf(fmaxf(fminf(x1.y, x2.y), fminf(y1.y, y2.y)), fmaxf(fminf(z1.y, z2.y), 0.0f));
-    const float f1 = fminf(fminf(fmaxf(x1.y, x2.y), fmaxf(y1.y, y2.y)), fminf(fmaxf(z1.y, z2.y), closest));
-    t0 = n0; t1 = n1;
-    h0 = n0 <= f0;
-    h1 = n1 <= f1;
-}
-
-// Möller–Trumbore (scene.cu:160-195, rt_device.h ray_triangle) with the early-outs folded into one
-// predicate: every quantity is computed for every lane and the accept test is the conjunction of
-// the reference's four reject tests, negated exactly as written (a NaN u, v or t rejects nothing,
-// as in the branchy form).  Same values, same outcome; no divergent exec-mask regions.  In a wave
-// of ~20 leaf lanes an early-out almost never skips work for all of them, so the nested branches
-// only cost their exec-mask bookkeeping (round 3, with the flat pop loop below: A/B teapot full
-// frame 6.94 -> 6.86 ms/pass over 5 rounds, 7.06 -> 6.86 over 3; 20 steps 7.24 -> 7.18, 7.27 -> 7.13).
-__device__ __forceinline__ bool ray_triangle_flat(V3 o, V3 d, V3 p1, V3 e1, V3 e2, float closest, float &t) {
-    const V3 h = cross(d, e2);
-    const float a = dot(h, e1);
-    const float f = 1 / a;
-    const V3 s = o - p1;
-    const float u = dot(s, h) * f;
-    const V3 q = cross(s, e1);
-    const float v = dot(d, q) * f;
-    t = dot(e2, q) * f;
-    const bool ok_a = a != 0;
-    const bool ok_u = !(u < 0 || u > 1);
-    const bool ok_v = !(v < 0 || u + v > 1);
-    const bool ok_t = !(t < kEps || t >= closest);
-    return ok_a & ok_u & ok_v & ok_t;
-}
-
-// Triangle range [ti, te) of a leaf ref (small leaves inline, big ones through big_leaves).
-__device__ __forceinline__ void leaf_range(const DevScene &S, uint32_t ref, int &ti, int &te) {
-    if (ref & kBigLeaf) {
-        const int2 be = S.big_leaves[ref & 0x3FFFFFFFu];
-        ti = be.x; te = be.y;
-    } else {
-        ti = (int)(ref & 0xFFFFFFu);
-        te = ti + (int)((ref >> 24) & 0x3Fu);
-    }
-}
-
-// Closest hit for the live slots [0, *live): the sphere loop (scene.cu:338-372) and
-// bvh_closest_hit_distance (scene.cu:134-241).  Persistent and wave-refilling: each wave takes
-// chunks of slots from a device queue (one atomic per chunk) and hands a new slot to a lane
-// as soon as that lane's ray is done, so incoherent rays of very different traversal lengths
-// do not leave most lanes idle.  Output per slot: {closest t, hit index} (index -1 = miss).
-// 8 waves per SIMD (<= 64 VGPRs): the one spill left is a lane constant reloaded only on the
-// overflow-stack path.  +2 % over the unconstrained 66 VGPRs (7 waves).
-#ifndef RT_TRACE_WPE
-#define RT_TRACE_WPE 8
-#endif
 #ifndef RT_FUSED_MAX_TRIS
 #define RT_FUSED_MAX_TRIS 4096        // fused reorder for scenes up to this many triangles (see enqueue_pass)
 #endif
 #ifndef RT_SORT_GRID
 #define RT_SORT_GRID 0                // cap on the reorder's hist/scatter grid (0: 8 blocks per CU)
 #endif
-#define RT_TRACE_ATTR __attribute__((amdgpu_waves_per_eu(RT_TRACE_WPE, RT_TRACE_WPE > 8 ? RT_TRACE_WPE : 8)))
 
+// Closest hit for the live slots [0, *live): the sphere loop (scene.cu:338-372) and
+// bvh_closest_hit_distance (scene.cu:134-241).  Persistent and wave-refilling: each wave takes
+// chunks of slots from a device queue (one atomic per chunk) and hands a new slot to a lane
+// as soon as that lane's ray is done, so incoherent rays of very different traversal lengths
+// do not leave most lanes idle.  Output per slot: {closest t, hit index} (index -1 = miss).
+// The slab pair, the flat triangle test and the leaf refs are rt_common.h's (shared with anyhit_kernel).
 template <bool SORTED, bool COUNT, int FIRST>
 __global__ __launch_bounds__(kBlock) RT_TRACE_ATTR void trace_kernel(DevScene S, PassArgs pa, const float4 *__restrict__ geo,
                                                        const uint32_t *__restrict__ live_count,
@@ -637,287 +505,6 @@ __global__ __launch_bounds__(kBlock) RT_TRACE_ATTR void trace_kernel(DevScene S,
         for (int i = 0; i < 14; i++)
             if (i != 10) atomicAdd(&g_prof[FIRST ? 0 : 1][i], prof[i]);
 #endif
-}
-
-// ---------------------------------------------------------------- ray queries (rt_query)
-// Caller rays (n x {o.xyz, d.xyz}, 24-B stride) -> the 32-B slots the traversal kernels read:
-// {o.xyz, d.x} {d.y, d.z, B, 1}.  B is the any-hit bound of the ray: tmax where tmax <= 1e30, otherwise
-// (larger, +inf, NaN, or no tmax array) 1e30; trace_kernel does not read it.  Block 0 also starts the
-// call: the live count, the queue shards and the work counters.
-__global__ __launch_bounds__(kBlock) void query_ingest_kernel(const float *__restrict__ rays, const float *__restrict__ tmax,
-                                                              uint32_t n, float4 *__restrict__ geo, uint32_t *__restrict__ live,
-                                                              uint32_t *__restrict__ queue, Counters *__restrict__ ctr) {
-    if (blockIdx.x == 0) {
-        if (threadIdx.x == 0) live[0] = n;
-        if (threadIdx.x < kQueues) queue[threadIdx.x * kQueueStride] = 0;
-        unsigned long long *w = reinterpret_cast<unsigned long long *>(ctr);
-        for (uint32_t k = threadIdx.x; k < kCtrSlots * (sizeof(Counters) / sizeof(unsigned long long)); k += kBlock) w[k] = 0;
-    }
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const float *r = rays + (size_t)i * 6;
-    float b = 1e30f;
-    if (tmax) {
-        const float v = tmax[i];
-        b = v <= 1e30f ? v : 1e30f;
-    }
-    geo[(size_t)i * 2] = make_float4(r[0], r[1], r[2], r[3]);
-    geo[(size_t)i * 2 + 1] = make_float4(r[4], r[5], b, 1.0f);
-}
-
-// trace_kernel's {t, index} records -> the caller's t[] and index[]; counts the hits (and those on spheres).
-__global__ __launch_bounds__(kBlock) void query_egest_kernel(const float2 *__restrict__ hits, uint32_t n, float *__restrict__ t,
-                                                             int32_t *__restrict__ index, int sphere_count,
-                                                             Counters *__restrict__ ctr) {
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    bool hit = false, sph = false;
-    if (i < n) {
-        const float2 h = hits[i];
-        const int idx = __float_as_int(h.y);
-        t[i] = h.x;
-        index[i] = idx;
-        hit = idx >= 0;
-        sph = hit && idx < sphere_count;
-    }
-    const unsigned long long nh = __popcll(__ballot(hit)), ns = __popcll(__ballot(sph));
-    Counters *cs = ctr + ((blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) & (kCtrSlots - 1));
-    if (lane_id() == 0 && nh) {
-        atomicAdd(&cs->hits, nh);
-        if (ns) atomicAdd(&cs->hits_sphere, ns);
-    }
-}
-
-// Any hit before the ray's bound B (rt_query_occluded): the reference traversal (scene.cu:338-372,
-// :134-241) with `closest` held at B and never updated; the answer is 1 iff some primitive is accepted.
-// The bound never shrinks, so whether a node is entered depends on (ray, B, node) alone and the answer is
-// an existence statement over a fixed node set: any visit order and an exit at the first accepted
-// primitive are exact.  Hence, unlike trace_kernel, which is bound to the reference's order:
-//   * the lane retires at the first accepted sphere or triangle;
-//   * of two hit children the near one is entered and the far one pushed;
-//   * the stack holds 4-B refs only (the push-time test `entry >= B` is the pop-time test, so a child that
-//     fails it is never pushed): 16 LDS entries + the scratch slot = 17 KB, deeper ones in `overflow`.
-// Queue, ballot refill, scalar root record, one record load per step and the literal slab fold for lanes
-// with a non-finite 1/d are trace_kernel's.  out[slot] = 0 or 1, stored at refill and at exit like hits[].
-// Counters (COUNT): Pn = nodes entered, Iv = internal nodes stepped, Tt = triangle tests, sphere tests up
-// to the first accepted sphere -- the oracle's numbers on unoccluded rays, order-dependent on occluded ones.
-constexpr int kAnyStackLds = 16;
-
-template <bool COUNT>
-__global__ __launch_bounds__(kBlock) RT_TRACE_ATTR void anyhit_kernel(DevScene S, const float4 *__restrict__ geo,
-                                                                      const uint32_t *__restrict__ live_count,
-                                                                      uint32_t *__restrict__ queue, uint8_t *__restrict__ out,
-                                                                      uint32_t *__restrict__ overflow,
-                                                                      Counters *__restrict__ ctr) {
-    __shared__ uint32_t stack[(kAnyStackLds + 1) * kBlock];   // + one scratch entry per lane
-    uint32_t *col = stack + threadIdx.x;
-    // entry e >= kAnyStackLds of this lane: overflow[(e - kAnyStackLds) * lanes + lane]
-    const uint32_t lanes = gridDim.x * kBlock, gl = blockIdx.x * kBlock + threadIdx.x;
-    const uint32_t L = __builtin_amdgcn_readfirstlane(*live_count);
-    const uint32_t waves = gridDim.x * (kBlock / 64);
-    const uint32_t chunk = min((uint32_t)kChunkMax, max((uint32_t)kChunkMin, (L / (4 * waves) + 63) & ~63u));
-    uint32_t shard = blockIdx.x % kQueues, tried = 0;
-    uint32_t q_next = 0, q_end = 0;     // this wave's current chunk (wave-uniform)
-    bool exhausted = false;
-    int slot = -1;                      // < 0: lane has no ray; <= -2: done with slot -2 - slot, `occ` not yet stored
-    V3 o{0, 0, 0}, d{0, 0, 0};
-    float ix = 0, iy = 0, iz = 0, B = 0;
-    bool finite_inv = true;
-    bool wave_nonfinite = false;
-    int sp = 0;
-    uint32_t ref = 0, occ = 0;
-    int ti = 0, te = 0;                 // the lane is in a leaf while ti < te
-    unsigned pn = 0, iv = 0, tt = 0, stn = 0, nocc = 0;
-    // One internal node's step: both children's slabs against B; a child is entered iff its box is hit
-    // and !(entry >= B) (scene.cu:196-225 with :147-152 applied at push time).  Returns whether the lane
-    // needs its next node from the stack.
-    auto node_step = [&](float4 a, float4 b, float4 c, uint2 kids) -> bool {
-        if (COUNT) iv++;
-        float t0, t1;
-        bool h0, h1;
-        slab_pair(a, b, c, o, ix, iy, iz, B, h0, h1, t0, t1);
-        if (__builtin_expect(wave_nonfinite, 0)) {
-            float u0, u1;
-            const bool g0 = slab(a.x, a.z, b.x, b.z, c.x, c.z, o, ix, iy, iz, B, u0);
-            const bool g1 = slab(a.y, a.w, b.y, b.w, c.y, c.w, o, ix, iy, iz, B, u1);
-            if (!finite_inv) { h0 = g0; h1 = g1; t0 = u0; t1 = u1; }
-        }
-        const bool e0 = h0 && !(t0 >= B), e1 = h1 && !(t1 >= B);
-        const bool both = e0 && e1, any = e0 || e1;
-        // next = child 1 iff it is the nearer of two entered children or the only one
-        const bool sel1 = e1 && (!e0 || t1 < t0);
-        const uint32_t next_ref = sel1 ? kids.y : kids.x, far_ref = sel1 ? kids.x : kids.y;
-        // written either way (above the top when not pushed; entry kAnyStackLds is a scratch slot)
-        col[min(sp, kAnyStackLds) * kBlock] = far_ref;
-        if (__builtin_expect(both && sp >= kAnyStackLds, 0)) overflow[(sp - kAnyStackLds) * lanes + gl] = far_ref;
-        if (both) sp++;
-        bool need = !any;
-        if (any) {
-            ref = next_ref;
-            if (COUNT) pn++;
-            if (ref & kLeaf) {
-                leaf_range(S, ref, ti, te);
-                need = ti == te;
-            }
-        }
-        return need;
-    };
-    // Pop: every entry on the stack is entered (it passed the bound test when it was pushed); an empty
-    // stack ends the ray unoccluded.
-    auto pop_loop = [&](bool need) {
-        while (need) {
-            const bool empty = sp == 0;
-            sp = empty ? 0 : sp - 1;
-            uint32_t e = col[min(sp, kAnyStackLds) * kBlock];
-            asm volatile("" : "+v"(e));   // keeps the LDS read an LDS read (see trace_kernel)
-            if (__builtin_expect(__ballot(sp >= kAnyStackLds) != 0, 0)) {   // wave-uniform, rare
-                if (sp >= kAnyStackLds) e = overflow[(sp - kAnyStackLds) * lanes + gl];
-            }
-            slot = empty ? -2 - slot : slot;
-            ref = empty ? ref : e;
-            if (COUNT) pn += empty ? 0u : 1u;
-            const bool leaf = !empty && (ref & kLeaf);
-            if (__builtin_expect(leaf && (ref & kBigLeaf), 0)) {
-                leaf_range(S, ref, ti, te);
-            } else {
-                ti = leaf ? (int)(ref & 0xFFFFFFu) : ti;
-                te = leaf ? ti + (int)((ref >> 24) & 0x3Fu) : te;
-            }
-            need = leaf && ti == te;
-        }
-    };
-    const bool root_internal = !(S.root_ref & kLeaf);
-    float4 ra{0, 0, 0, 0}, rb{0, 0, 0, 0}, rc{0, 0, 0, 0};
-    uint2 rk{0, 0};
-    if (root_internal) {
-        const float4 *rr = S.nodes + (size_t)S.root_ref * 4;
-        const float4 x0 = rr[0], x1 = rr[1], x2 = rr[2];
-        const uint2 k = *reinterpret_cast<const uint2 *>(rr + 3);
-#define RT_U(v) __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)))
-        ra = make_float4(RT_U(x0.x), RT_U(x0.y), RT_U(x0.z), RT_U(x0.w));
-        rb = make_float4(RT_U(x1.x), RT_U(x1.y), RT_U(x1.z), RT_U(x1.w));
-        rc = make_float4(RT_U(x2.x), RT_U(x2.y), RT_U(x2.z), RT_U(x2.w));
-#undef RT_U
-        rk = make_uint2(__builtin_amdgcn_readfirstlane(k.x), __builtin_amdgcn_readfirstlane(k.y));
-    }
-    while (true) {
-        // ---- refill idle lanes (wave-uniform control flow)
-        unsigned long long idle = __ballot(slot < 0);
-        if (!exhausted && __popcll(idle) >= kRefill) {
-            if (slot <= -2) {             // answers of the lanes that finished since the last refill
-                out[-2 - slot] = (uint8_t)occ;
-                nocc += occ;
-                slot = -1;
-            }
-            bool fresh = false;
-            while (idle && !exhausted) {
-                if (q_next >= q_end) {
-                    const uint32_t seg_lo = (uint32_t)(((uint64_t)L * shard) / kQueues);
-                    const uint32_t seg_hi = (uint32_t)(((uint64_t)L * (shard + 1)) / kQueues);
-                    uint32_t c = 0;
-                    if (lane_id() == 0) c = atomicAdd(queue + shard * kQueueStride, chunk);
-                    c = __builtin_amdgcn_readfirstlane(__shfl(c, 0)) + seg_lo;
-                    if (c >= seg_hi) {
-                        shard = (shard + 1) % kQueues;
-                        if (++tried == kQueues) exhausted = true;
-                        continue;
-                    }
-                    q_next = c;
-                    q_end = min(c + chunk, seg_hi);
-                }
-                const uint32_t avail = q_end - q_next;
-                const uint32_t r = rank_below(idle);
-                const bool take = slot < 0 && r < avail;
-                const unsigned long long took = __ballot(take);
-                if (take) { slot = (int)(q_next + r); fresh = true; }
-                q_next += (uint32_t)__popcll(took);
-                idle &= ~took;
-            }
-            if (fresh) {
-                const float4 *rp = geo + (size_t)slot * 2;
-                const float4 r0 = rp[0], r1 = rp[1];
-                o = v3(r0.x, r0.y, r0.z);
-                d = v3(r0.w, r1.x, r1.y);
-                B = r1.z;
-                ix = 1 / d.x; iy = 1 / d.y; iz = 1 / d.z;
-                finite_inv = __builtin_isfinite(ix) && __builtin_isfinite(iy) && __builtin_isfinite(iz);
-                occ = 0;
-                for (int i = 0; i < S.sphere_count; i++) {
-                    const float4 sph = S.spheres[i];
-                    float t;
-                    if (COUNT) stn++;
-                    if (ray_sphere(o, d, v3(sph.x, sph.y, sph.z), sph.w, B, t)) { occ = 1; break; }
-                }
-                ref = S.root_ref;
-                sp = 0;
-                ti = te = 0;
-                // the root is popped with distance 0: entered iff !(0 >= B) (scene.cu:147-152)
-                bool done = occ || 0.0f >= B;
-                if (!done) {
-                    if (COUNT) pn++;
-                    if (ref & kLeaf) {
-                        leaf_range(S, ref, ti, te);
-                        done = ti == te;    // no triangles at all: spheres only
-                    }
-                }
-                if (done) {
-                    out[slot] = (uint8_t)occ;
-                    nocc += occ;
-                    slot = -1;
-                }
-            }
-            wave_nonfinite = __ballot(slot >= 0 && !finite_inv) != 0;
-            if (root_internal && __ballot(fresh && slot >= 0)) {   // the fresh lanes' root step
-                bool need = false;
-                if (fresh && slot >= 0) need = node_step(ra, rb, rc, rk);
-                pop_loop(need);
-            }
-        }
-        if (!__ballot(slot >= 0)) {
-            if (exhausted) break;
-            continue;
-        }
-        if (slot < 0) continue;
-        // ---- one step: one triangle test of the current leaf, or one internal node; the record is read
-        // through the same loads either way (see trace_kernel)
-        bool need = false;
-        const bool in_leaf = ti < te;
-        const float4 *rec = in_leaf ? S.tris + (size_t)ti * 3 : S.nodes + (size_t)ref * 4;
-        const float4 a = rec[0], b = rec[1], c = rec[2];
-        uint2 kids = make_uint2(0, 0);
-        if (!in_leaf) kids = *reinterpret_cast<const uint2 *>(rec + 3);
-        if (in_leaf) {
-            if (COUNT) tt++;
-            float t;
-            const bool hit = ray_triangle_flat(o, d, v3(a.x, a.y, a.z), v3(a.w, b.x, b.y), v3(b.z, b.w, c.x), B, t);
-            ti++;
-            if (hit) {                    // the first accepted triangle ends the ray
-                occ = 1;
-                slot = -2 - slot;
-                ti = te = 0;
-            } else {
-                need = ti == te;
-            }
-        } else {
-            need = node_step(a, b, c, kids);
-        }
-        pop_loop(need);
-    }
-    if (slot <= -2) {
-        out[-2 - slot] = (uint8_t)occ;
-        nocc += occ;
-    }
-    Counters *cs = ctr + ((blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) & (kCtrSlots - 1));
-    const unsigned long long no = wave_sum(nocc);
-    if (COUNT) {
-        const unsigned long long a = wave_sum(pn), b = wave_sum(iv), t = wave_sum(tt), s = wave_sum(stn);
-        if (lane_id() == 0) {
-            atomicAdd(&cs->pn, a);
-            atomicAdd(&cs->iv, b);
-            atomicAdd(&cs->tt, t);
-            atomicAdd(&cs->st, s);
-        }
-    }
-    if (lane_id() == 0 && no) atomicAdd(&cs->hits, no);
 }
 
 // One ray's shading (scene.cu:376-485) at `slot`: environment lookup on a miss, otherwise
@@ -1655,18 +1242,6 @@ __global__ __launch_bounds__(kBlock) void add4_kernel(float *__restrict__ img, c
 }
 
 // ==================================================================== host side
-int hip_fail(hipError_t e, const char *what) {
-    return rtamd::fail(e == hipErrorOutOfMemory ? RT_E_OOM : RT_E_HIP,
-                       std::string("Error ") + what + " " + hipGetErrorString(e));
-}
-#define HIPCHK(call)                                          \
-    do {                                                      \
-        const hipError_t e_ = (call);                         \
-        if (e_ != hipSuccess) return hip_fail(e_, #call);     \
-    } while (0)
-
-inline int blocks_for(int64_t n) { return (int)((n + kBlock - 1) / kBlock); }
-
 // Hardware queues: HIP gives a process GPU_MAX_HW_QUEUES in-order hardware queues per device
 // (4 by default) and maps further streams onto them round-robin, and two pass streams that share a queue
 // run their passes one after the other.  The renderer keeps up to 20 passes in flight on streams of their
@@ -1683,31 +1258,23 @@ int queues_granted() {
     return n > 0 ? n : 4;                   // HIP's default
 }
 
-template <class T>
-struct DevBuf {
-    T *p = nullptr;
-    size_t n = 0;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t count) {
-        if (p) { (void)hipFree(p); p = nullptr; }
-        n = count;
-        if (!count) return RT_OK;
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&p), count * sizeof(T)));
-        return RT_OK;
-    }
-    // `pad` zeroed elements after the copied ones (readable slack for over-wide loads)
-    int upload(const void *src, size_t count, hipStream_t s, size_t pad = 0) {
-        int rc = alloc(count + pad);
-        if (rc) return rc;
-        if (count) HIPCHK(hipMemcpyAsync(p, src, count * sizeof(T), hipMemcpyHostToDevice, s));
-        if (pad) HIPCHK(hipMemsetAsync(p + count, 0, pad * sizeof(T), s));
-        return RT_OK;
-    }
-};
-
-bool is_leaf(const rt_bvh_node &nd) { return nd.child2 <= nd.child1; }   // scene.cu:859
-
 }  // namespace
+
+// The closest-hit launch of rt_query.hip (rt_common.h): trace_kernel is compiled in this file only.
+int rtamd::trace_closest_blocks_per_cu(int &per_cu) {
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_kernel<false, false, 0>, kBlock, 0));
+    return RT_OK;
+}
+void rtamd::launch_trace_closest(bool count, int grid, hipStream_t s, const DevScene &ds, const float4 *geo,
+                                 const uint32_t *live, uint32_t *queue, float2 *hits, uint32_t *overflow, Counters *ctr) {
+    const PassArgs pa{1, 0u, FastDiv::of(1), FastDiv::of((uint32_t)ds.width), SlotMap::identity()};
+    if (count)
+        hipLaunchKernelGGL((trace_kernel<false, true, 0>), dim3(grid), dim3(kBlock), 0, s, ds, pa, geo, live, queue, hits,
+                           overflow, ctr, nullptr);
+    else
+        hipLaunchKernelGGL((trace_kernel<false, false, 0>), dim3(grid), dim3(kBlock), 0, s, ds, pa, geo, live, queue, hits,
+                           overflow, ctr, nullptr);
+}
 
 // Device state of one in-flight pass: its own stream, ray state, reorder buffers and queues.
 // Phase timing of renderer setup, printed to stderr when RTAMD_TIMING is set.
@@ -1783,7 +1350,6 @@ struct PassCtx {
 };
 
 struct rt_renderer {
-    int device = 0;
     bool sort = true, counters = false;
     int tile_count = 1, tile_index = 0, tile_rows = 8;   // pixel-tile sharding (rt_opts)
     // per-bounce HIP events for rt_stats.process_ms / sort_ms (rt_renderer_set_event_timing): four
@@ -1806,13 +1372,8 @@ struct rt_renderer {
     bool home = false;
     uint32_t home_base = 0;
     int width = 0, height = 0, spp = 0, bounces = 0;
-    DevScene ds{};
-    DevBuf<float4> spheres, tris, mats, nodes;
-    DevBuf<uint16_t> mat_idx;
-    DevBuf<int2> big;
-    std::vector<int> node_rec;        // node -> child-pair record (-1: leaf), kept for a scene-only renderer (refit)
-    DevBuf<float> env, fb;
-    DevBuf<Counters> ctr;
+    SceneDev scene;                   // the device arrays, the DevScene the kernels take, the work counters
+    DevBuf<float> fb;
     DevBuf<unsigned long long> tspans;   // per run: [pass][bounce] trace-launch wall-clock spans (event timing on)
     int wall_khz = 0;                    // device wall clock rate (wall_clock64 ticks per ms)
     // rt_renderer_launch_profile: the last event-timed run's first pass, per bounce
@@ -1832,15 +1393,14 @@ struct rt_renderer {
     int trace_blocks_max = 0;         // all resident trace workgroups (the overflow stacks are sized for it)
     int nctx = 1;                     // pass contexts allocated (passes in flight)
     int inflight_cap = kInflight;     // passes in flight allowed (kInflight, or RTAMD_INFLIGHT)
-    int cus = 0;
     hipEvent_t t_begin = nullptr, t_end = nullptr;
 
     ~rt_renderer() {
-        (void)hipSetDevice(device);
+        (void)hipSetDevice(scene.device);
         if (run_pending && t_end) (void)hipEventSynchronize(t_end);   // an async run never finished
         for (hipEvent_t e : pass_done) (void)hipEventDestroy(e);
         if (xcomm) {
-            (void)hipSetDevice(device);
+            (void)hipSetDevice(scene.device);
             // after a failed run, collectives may be pending that a dead peer never joins: abort the
             // communicator first (that ends them), and only then drain the streams
             if (failed) (void)ncclCommAbort(static_cast<ncclComm_t>(xcomm));
@@ -1878,9 +1438,9 @@ struct rt_renderer {
         return rows * width;
     }
 
-    // passes = false: scene only (rt_trace_rays), no pass contexts
-    int init(const rt_scene *sc, const rt_opts *o, bool passes = true) {
-        device = o->device;
+    // o: checked by resolve_opts
+    int init(const rt_scene *sc, const rt_opts *o) {
+        scene.device = o->device;       // the destructor's, should init stop before scene.init
         sort = o->sort != 0;
         counters = o->collect_counters != 0;
         tile_count = std::max(1, o->tile_count);
@@ -1895,8 +1455,6 @@ struct rt_renderer {
         }
         inline_hits = fused && sc->triangle_count == 0;
         if (const char *f = std::getenv("RTAMD_INLINE")) inline_hits = fused && std::atoi(f) != 0 && sc->triangle_count == 0;
-        if (tile_index < 0 || tile_index >= tile_count)
-            return rtamd::fail(RT_E_INVALID, "tile_index outside [0, tile_count)");
         if (tsort()) {                  // per-bounce exchange between the kernels: the plain
             fused = false;              // shade/scatter pair only
             fused_upto = -1;
@@ -1907,7 +1465,7 @@ struct rt_renderer {
         spp = sc->ray_count;
         bounces = sc->bounces;
         InitTimer tm;
-        HIPCHK(hipSetDevice(device));
+        HIPCHK(hipSetDevice(o->device));
         tm.mark("hipSetDevice");
         // streams cost ~3.6 ms each to create and ~2 ms to destroy: context 0's now, the other
         // contexts' once the number of passes in flight is known
@@ -1917,88 +1475,16 @@ struct rt_renderer {
         HIPCHK(hipEventCreate(&t_end));
         hipStream_t s0 = stream();
         int rc;
-        // Child-pair node records.  Record numbering: the two children of a node get adjacent
-        // records (an even/odd pair, one 128-B line), so stepping into one child brings in its
-        // sibling's record too, which the stack usually visits next; pairs are handed out in
-        // depth-first order so a subtree's records stay close.  Layout only: the traversal
-        // order is unchanged.
-        const int nn = sc->bvh_node_count;
-        std::vector<int> rec(nn, -1);
-        int nrec = 0;
-        if (nn > 0 && !is_leaf(sc->bvh[0])) {
-            rec[0] = 0;
-            nrec = 2;                   // record 1: padding, the root has no sibling
-            // (node, depth of that internal node): a visit of an internal node at depth k can leave
-            // k + 1 entries on the traversal stack, which holds kStackMax (the reference's
-            // MAX_BVH_DEPTH 30 gives at most 30, scene.cu:10); a deeper caller-supplied BVH would
-            // run past the per-lane overflow stack, so it is refused here
-            std::vector<std::pair<int, int>> todo{{0, 0}};
-            int visited = 0;
-            while (!todo.empty()) {
-                const int i = todo.back().first, depth = todo.back().second;
-                todo.pop_back();
-                if (++visited > nn) return rtamd::fail(RT_E_INVALID, "BVH is not a tree");
-                if (depth + 1 > kStackMax)
-                    return rtamd::fail(RT_E_INVALID, "BVH deeper than the traversal stack (" + std::to_string(kStackMax) +
-                                                     " internal levels)");
-                const rt_bvh_node &nd = sc->bvh[i];
-                if (nd.child1 < 0 || nd.child2 >= nn || nd.child1 >= nn || nd.child2 < 0)
-                    return rtamd::fail(RT_E_INVALID, "BVH child index out of range");
-                const bool in1 = !is_leaf(sc->bvh[nd.child1]), in2 = !is_leaf(sc->bvh[nd.child2]);
-                if (in1) rec[nd.child1] = nrec;
-                if (in2) rec[nd.child2] = nrec + 1;
-                if (in1 || in2) nrec += 2;
-                if (in2) todo.push_back({nd.child2, depth + 1});   // child1's subtree first (depth-first)
-                if (in1) todo.push_back({nd.child1, depth + 1});
-            }
-        }
-        std::vector<int2> big_h;
-        auto ref_of = [&](int c) -> uint32_t {
-            const rt_bvh_node &nd = sc->bvh[c];
-            if (!is_leaf(nd)) return (uint32_t)rec[c];
-            const int begin = nd.child2, count = nd.child1 - nd.child2;
-            if (count < 64 && begin < (1 << 24)) return kLeaf | ((uint32_t)count << 24) | (uint32_t)begin;
-            big_h.push_back(make_int2(nd.child2, nd.child1));
-            return kLeaf | kBigLeaf | (uint32_t)(big_h.size() - 1);
-        };
-        std::vector<float4> rec_h((size_t)std::max(nrec, 1) * 4);
-        for (int i = 0; i < nn; i++) {
-            if (rec[i] < 0) continue;
-            const rt_bvh_node &nd = sc->bvh[i];
-            const rt_bvh_node &l = sc->bvh[nd.child1], &r = sc->bvh[nd.child2];
-            float4 *q = &rec_h[(size_t)rec[i] * 4];
-            // the two children's bounds interleaved per plane, so one packed-fp32 op handles both
-            q[0] = make_float4(l.min_bound.x, r.min_bound.x, l.min_bound.y, r.min_bound.y);
-            q[1] = make_float4(l.min_bound.z, r.min_bound.z, l.max_bound.x, r.max_bound.x);
-            q[2] = make_float4(l.max_bound.y, r.max_bound.y, l.max_bound.z, r.max_bound.z);
-            const uint32_t a = ref_of(nd.child1), b = ref_of(nd.child2);
-            std::memcpy(&q[3].x, &a, 4);
-            std::memcpy(&q[3].y, &b, 4);
-            q[3].z = q[3].w = 0.0f;
-        }
-        ds.root_ref = nn > 0 ? ref_of(0) : (kLeaf | 0u);
-        if (big_h.empty()) big_h.push_back(make_int2(0, 0));
-        if (!passes) node_rec = rec;
-        if ((rc = spheres.upload(sc->spheres, sc->sphere_count, s0))) return rc;
-        // one float4 of slack: traversal reads 64 B at a triangle record (48 B) like at a node
-        if ((rc = tris.upload(sc->triangles, (size_t)sc->triangle_count * 3, s0, 1))) return rc;
-        if ((rc = mats.upload(sc->materials, (size_t)sc->material_count * 3, s0))) return rc;
-        if ((rc = mat_idx.upload(sc->material_indices, (size_t)sc->sphere_count + sc->triangle_count, s0))) return rc;
-        if ((rc = nodes.upload(rec_h.data(), rec_h.size(), s0))) return rc;
-        if ((rc = big.upload(big_h.data(), big_h.size(), s0))) return rc;
-        if ((rc = env.upload(sc->environment_map, (size_t)sc->environment_map_width * sc->environment_map_height * 3, s0)))
-            return rc;
+        if ((rc = scene.init(sc, o->device, s0))) return rc;
         const int64_t pixels = (int64_t)width * height;
         const int64_t max_rays = pixels * std::min(20, std::max(1, spp));
         if (max_rays > 0x7fffffff / 3) return rtamd::fail(RT_E_INVALID, "image too large for 32-bit ray indices");
         if ((rc = fb.alloc((size_t)pixels * 3))) return rc;
-        if ((rc = ctr.alloc(kCtrSlots))) return rc;
         int per_cu = 0;
-        HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
         tm.mark("scene upload");
         HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_kernel<true, false, false>, kBlock, 0));
         tm.mark("occupancy query");
-        trace_blocks_max = std::max(1, cus * std::max(1, per_cu));
+        trace_blocks_max = std::max(1, scene.cus * std::max(1, per_cu));
         trace_blocks = trace_blocks_max;
         const int tiles = tile_stride(max_rays);
         home = sort && !tiled() && bounces >= 2 && (fused || fused_upto >= 0);
@@ -2020,11 +1506,11 @@ struct rt_renderer {
         cap = std::min<size_t>(cap, (size_t)queues_granted());
         inflight_cap = (int)cap;
         if (pass_hint > 0) cap = std::min<size_t>(cap, (size_t)pass_hint);   // a one-shot render of fewer passes
-        nctx = !passes ? 0 : (int)std::min<size_t>({cap, (size_t)std::max(1, pass_count()),
+        nctx = (int)std::min<size_t>({cap, (size_t)std::max(1, pass_count()),
                                                     std::max<size_t>(1, mem_free / 2 / ctx_bytes)});
         // Pixel tiles with the reorder on: the exchange order follows the passes in flight, which
         // must therefore be the same on every owner; it may not depend on this device's free memory.
-        if (passes && tsort() && (size_t)nctx < std::min<size_t>(cap, (size_t)std::max(1, pass_count())))
+        if (tsort() && (size_t)nctx < std::min<size_t>(cap, (size_t)std::max(1, pass_count())))
             return rtamd::fail(RT_E_OOM, "pixel tiles with sort on: device memory holds only " + std::to_string(nctx) +
                                              " passes in flight; set RTAMD_INFLIGHT to the same lower value on every owner");
         const int inflight = nctx;
@@ -2060,26 +1546,6 @@ struct rt_renderer {
         }
         tm.mark("pass contexts");
         HIPCHK(hipMemsetAsync(fb.p, 0, fb.n * sizeof(float), s0));
-        ds.spheres = spheres.p;
-        ds.tris = tris.p;
-        ds.mat_idx = mat_idx.p;
-        ds.mats = mats.p;
-        ds.nodes = nodes.p;
-        ds.big_leaves = big.p;
-        ds.env = env.p;
-        ds.sphere_count = sc->sphere_count;
-        ds.env_w = sc->environment_map_width;
-        ds.env_h = sc->environment_map_height;
-        ds.width = width;
-        ds.height = height;
-        ds.cam = v3(sc->camera_position.x, sc->camera_position.y, sc->camera_position.z);
-        ds.tl = v3(sc->near_plane_top_left.x, sc->near_plane_top_left.y, sc->near_plane_top_left.z);
-        ds.sr = v3(sc->scaled_right.x, sc->scaled_right.y, sc->scaled_right.z);
-        ds.su = v3(sc->scaled_up.x, sc->scaled_up.y, sc->scaled_up.z);
-        ds.min_coord = v3(sc->min_coord.x, sc->min_coord.y, sc->min_coord.z);
-        ds.inv_dim = v3(sc->inv_dimensions.x, sc->inv_dimensions.y, sc->inv_dimensions.z);
-        ds.inv_w = sc->inv_width;
-        ds.inv_h = sc->inv_height;
         HIPCHK(hipStreamSynchronize(s0));
         tm.mark("sync");
         tm.report();
@@ -2099,10 +1565,10 @@ struct rt_renderer {
         const int grid = blocks_for(n);
         const int tiles = tile_stride(n);     // counts stride; a launch's tiles follow its live count
         const int tgrid = std::min(grid, trace_blocks);
-        const int sgrid = std::min(grid, cus * RT_SHADE_BPC);
+        const int sgrid = std::min(grid, scene.cus * RT_SHADE_BPC);
         // tile-stride reorder kernels on at most 8 blocks per CU: in the tail bounces a block per
         // possible tile dispatched ~10^4 empty workgroups per launch (A/B: +0.3-0.5 %)
-        const int sort_grid = std::max(1, std::min(max_tiles(n), RT_SORT_GRID > 0 ? RT_SORT_GRID : cus * 8));
+        const int sort_grid = std::max(1, std::min(max_tiles(n), RT_SORT_GRID > 0 ? RT_SORT_GRID : scene.cus * 8));
         hipStream_t st = c.stream;
         int cur = 0;
         if (n == 0) {                           // a tile owner with no stripe of this image
@@ -2137,21 +1603,22 @@ struct rt_renderer {
 #define RT_PROCESS3(SORTED, COUNT, FIRST)                                                                         \
     do {                                                                                                         \
         if (!inline_hits)                                                                                        \
-            hipLaunchKernelGGL((trace_kernel<SORTED, COUNT, FIRST>), dim3(tgrid), dim3(kBlock), 0, st, ds, pa,    \
-                               c.geo[cur].p, lv, q, c.hits.p, c.overflow.p, ctr.p, tspan ? tspan + kSpanWords * b : nullptr); \
+            hipLaunchKernelGGL((trace_kernel<SORTED, COUNT, FIRST>), dim3(tgrid), dim3(kBlock), 0, st, scene.ds, pa, \
+                               c.geo[cur].p, lv, q, c.hits.p, c.overflow.p, scene.ctr.p,                         \
+                               tspan ? tspan + kSpanWords * b : nullptr);                                        \
         if (em) HIPCHK(hipEventRecord(em, st));                                                                  \
         if (inline_hits)                                                                                         \
             hipLaunchKernelGGL((shade_kernel<SORTED, COUNT, FIRST, true, true>), dim3(sgrid), dim3(kBlock), 0, st,\
-                               ds, pa, c.geo[cur].p, c.tz[cur].p, c.rid[cur].p, c.acc.p, c.bkt.p, lv, c.hits.p,  \
-                               seed_term, (int)last, ctr.p, nullptr, hist, tiles, (int)(home && b == 0));        \
+                               scene.ds, pa, c.geo[cur].p, c.tz[cur].p, c.rid[cur].p, c.acc.p, c.bkt.p, lv, c.hits.p, \
+                               seed_term, (int)last, scene.ctr.p, nullptr, hist, tiles, (int)(home && b == 0));  \
         else if (fused || b <= fused_upto)                                                                       \
             hipLaunchKernelGGL((shade_kernel<SORTED, COUNT, FIRST, true, false>), dim3(sgrid), dim3(kBlock), 0, \
-                               st, ds, pa, c.geo[cur].p, c.tz[cur].p, c.rid[cur].p, c.acc.p, c.bkt.p, lv, c.hits.p,      \
-                               seed_term, (int)last, ctr.p, nullptr, hist, tiles, (int)(home && b == 0));        \
+                               st, scene.ds, pa, c.geo[cur].p, c.tz[cur].p, c.rid[cur].p, c.acc.p, c.bkt.p, lv, c.hits.p, \
+                               seed_term, (int)last, scene.ctr.p, nullptr, hist, tiles, (int)(home && b == 0));  \
         else                                                                                                     \
             hipLaunchKernelGGL((shade_kernel<SORTED, COUNT, FIRST, false, false>), dim3(sgrid), dim3(kBlock), 0, \
-                               st, ds, pa, c.geo[cur].p, c.tz[cur].p, c.rid[cur].p, c.acc.p, c.bkt.p, lv, c.hits.p,      \
-                               seed_term, (int)last, ctr.p, nullptr, hist, tiles, (int)(home && b == 0));        \
+                               st, scene.ds, pa, c.geo[cur].p, c.tz[cur].p, c.rid[cur].p, c.acc.p, c.bkt.p, lv, c.hits.p, \
+                               seed_term, (int)last, scene.ctr.p, nullptr, hist, tiles, (int)(home && b == 0));  \
     } while (0)
 #define RT_PROCESS(SORTED, COUNT)                                                                                \
     do {                                                                                                         \
@@ -2184,7 +1651,7 @@ struct rt_renderer {
                                    c.sort_offsets.p, c.sort_totals.p, c.live.p + b + 1);
                 if (fused || b <= fused_upto) {
 #define RT_FSC2(SO, FI, IN)                                                                                      \
-    hipLaunchKernelGGL((sort_scatter_shade_kernel<SO, FI, IN>), dim3(sort_grid), dim3(kBlock), 0, st, ds, pa,     \
+    hipLaunchKernelGGL((sort_scatter_shade_kernel<SO, FI, IN>), dim3(sort_grid), dim3(kBlock), 0, st, scene.ds, pa, \
                        c.bkt.p, c.geo[cur].p, c.tz[cur].p, c.rid[cur].p, c.hits.p, seed_term, lv, tiles,          \
                        c.sort_offsets.p, c.sort_totals.p, c.geo[1 - cur].p, c.tz[1 - cur].p, c.rid[1 - cur].p,    \
                        c.acc.p, home && b == 0 ? c.home_of.p : nullptr, home_base)
@@ -2284,7 +1751,7 @@ struct rt_renderer {
         const PassArgs pa = tsort_args(c);
         const int grid = blocks_for(c.t_n);
         const int tgrid = std::max(1, std::min(grid, trace_blocks));
-        const int sgrid = std::max(1, std::min(grid, cus * RT_SHADE_BPC));
+        const int sgrid = std::max(1, std::min(grid, scene.cus * RT_SHADE_BPC));
         const uint32_t seed_term = 279220567u * (uint32_t)(c.t_rem * 20 + b);
         const uint32_t *lv = c.live.p + b;
         uint32_t *q = c.queue.p + (size_t)b * kQueues * kQueueStride;
@@ -2293,24 +1760,24 @@ struct rt_renderer {
         if (!last) {
             // zero G and L over the global live prefix, even for an owner without rays: its zeros are
             // its part of the sum (an owner with no stripe, e.g. more owners than stripes)
-            const int zgrid = std::max(1, std::min(blocks_for((int64_t)(c.t_lg + 15) / 16), cus * 8));
+            const int zgrid = std::max(1, std::min(blocks_for((int64_t)(c.t_lg + 15) / 16), scene.cus * 8));
             hipLaunchKernelGGL(zero_bytes_kernel, dim3(zgrid), dim3(kBlock), 0, st, c.gbytes.p, c.lbytes.p, c.glive.p);
         }
         if (c.t_n == 0) return RT_OK;
 #define RT_TS(COUNT)                                                                                           \
     do {                                                                                                           \
         if (b == 0) {                                                                                              \
-            hipLaunchKernelGGL((trace_kernel<true, COUNT, 2>), dim3(tgrid), dim3(kBlock), 0, st, ds, pa,            \
-                               c.geo[cur].p, lv, q, c.hits.p, c.overflow.p, ctr.p, nullptr);                       \
-            hipLaunchKernelGGL((shade_kernel<true, COUNT, 2, false, false>), dim3(sgrid), dim3(kBlock), 0, st, ds, \
+            hipLaunchKernelGGL((trace_kernel<true, COUNT, 2>), dim3(tgrid), dim3(kBlock), 0, st, scene.ds, pa,           \
+                               c.geo[cur].p, lv, q, c.hits.p, c.overflow.p, scene.ctr.p, nullptr);                       \
+            hipLaunchKernelGGL((shade_kernel<true, COUNT, 2, false, false>), dim3(sgrid), dim3(kBlock), 0, st, scene.ds, \
                                pa, c.geo[cur].p, c.tz[cur].p, c.rid[cur].p, c.acc.p, c.bkt.p, lv, c.hits.p,         \
-                               seed_term, last, ctr.p, nullptr);                                                   \
+                               seed_term, last, scene.ctr.p, nullptr);                                                   \
         } else {                                                                                                   \
-            hipLaunchKernelGGL((trace_kernel<true, COUNT, 0>), dim3(tgrid), dim3(kBlock), 0, st, ds, pa,            \
-                               c.geo[cur].p, lv, q, c.hits.p, c.overflow.p, ctr.p, nullptr);                       \
-            hipLaunchKernelGGL((shade_kernel<true, COUNT, 0, false, false>), dim3(sgrid), dim3(kBlock), 0, st, ds, \
+            hipLaunchKernelGGL((trace_kernel<true, COUNT, 0>), dim3(tgrid), dim3(kBlock), 0, st, scene.ds, pa,           \
+                               c.geo[cur].p, lv, q, c.hits.p, c.overflow.p, scene.ctr.p, nullptr);                       \
+            hipLaunchKernelGGL((shade_kernel<true, COUNT, 0, false, false>), dim3(sgrid), dim3(kBlock), 0, st, scene.ds, \
                                pa, c.geo[cur].p, c.tz[cur].p, c.rid[cur].p, c.acc.p, c.bkt.p, lv, c.hits.p,         \
-                               seed_term, last, ctr.p, c.gslot[cur].p);                                            \
+                               seed_term, last, scene.ctr.p, c.gslot[cur].p);                                            \
         }                                                                                                          \
     } while (0)
         if (counters) RT_TS(true); else RT_TS(false);
@@ -2354,7 +1821,7 @@ struct rt_renderer {
             if (rc) return rtamd::fail(RT_E_INVALID, "tile exchange callback failed (" + std::to_string(rc) + ")");
         }
         const int tg = c.t_tiles_g;
-        const int ggrid = std::max(1, std::min(max_tiles((int64_t)lg), cus * 8));
+        const int ggrid = std::max(1, std::min(max_tiles((int64_t)lg), scene.cus * 8));
         // global: buckets of every live slot -> new global slots of this owner's slots (newpos) and
         // the next global live count
         hipLaunchKernelGGL(gsort_hist_kernel, dim3(ggrid), dim3(kBlock), 0, st, c.gbytes.p, c.glive.p, tg,
@@ -2370,7 +1837,7 @@ struct rt_renderer {
         // each carrying its new global slot
         const uint32_t *lv = c.live.p + b;
         const int tiles = tile_stride(c.t_n);
-        const int sort_grid = std::max(1, std::min(max_tiles(c.t_n), RT_SORT_GRID > 0 ? RT_SORT_GRID : cus * 8));
+        const int sort_grid = std::max(1, std::min(max_tiles(c.t_n), RT_SORT_GRID > 0 ? RT_SORT_GRID : scene.cus * 8));
         const int cur = c.t_cur;
         hipLaunchKernelGGL(sort_hist_kernel, dim3(sort_grid), dim3(kBlock), 0, st, c.bkt.p, lv, tiles, c.sort_counts.p);
         hipLaunchKernelGGL(sort_scan_kernel, dim3(kBuckets), dim3(kBlock), 0, st, c.sort_counts.p, lv, tiles,
@@ -2398,59 +1865,6 @@ struct rt_renderer {
                                dim3(kBlock), 0, st, c.acc.p, c.t_rtc, (int)tpix, sums, pix);
         }
         HIPCHK(hipGetLastError());
-        return RT_OK;
-    }
-
-    // Closest hit of n caller rays (o.xyz, d.xyz; d unit length like every ray of the render):
-    // the sphere loop and BVH traversal of one bounce (scene.cu:338-372, :134-241) through the
-    // same trace_kernel as the render, without shading.
-    int trace_rays(const float *rays, int n, float *t_out, int32_t *index_out, rt_stats *st) {
-        HIPCHK(hipSetDevice(device));
-        if (n <= 0) return RT_OK;
-        hipStream_t s0 = stream();
-        std::vector<float4> g((size_t)n * 2);
-        for (int i = 0; i < n; i++) {
-            const float *r = rays + (size_t)i * 6;
-            g[(size_t)i * 2] = make_float4(r[0], r[1], r[2], r[3]);
-            g[(size_t)i * 2 + 1] = make_float4(r[4], r[5], 1.0f, 1.0f);
-        }
-        DevBuf<float4> geo;
-        DevBuf<uint32_t> live, queue, overflow;
-        DevBuf<float2> hits;
-        int rc;
-        if ((rc = geo.upload(g.data(), g.size(), s0))) return rc;
-        if ((rc = live.alloc(1)) || (rc = queue.alloc((size_t)kQueues * kQueueStride)) ||
-            (rc = hits.alloc((size_t)n)) || (rc = overflow.alloc((size_t)trace_blocks * kBlock * 2 * (kStackMax - kStackLds))))
-            return rc;
-        HIPCHK(hipMemsetAsync(queue.p, 0, queue.n * sizeof(uint32_t), s0));
-        const uint32_t nn = (uint32_t)n;
-        HIPCHK(hipMemcpyAsync(live.p, &nn, sizeof(nn), hipMemcpyHostToDevice, s0));
-        HIPCHK(hipMemsetAsync(ctr.p, 0, sizeof(Counters) * kCtrSlots, s0));
-        const PassArgs pa{1, 0u, FastDiv::of(1), FastDiv::of((uint32_t)width), SlotMap::identity()};
-        const int tgrid = std::min(blocks_for(n), trace_blocks);
-        if (counters)
-            hipLaunchKernelGGL((trace_kernel<false, true, false>), dim3(tgrid), dim3(kBlock), 0, s0, ds, pa, geo.p,
-                               live.p, queue.p, hits.p, overflow.p, ctr.p, nullptr);
-        else
-            hipLaunchKernelGGL((trace_kernel<false, false, false>), dim3(tgrid), dim3(kBlock), 0, s0, ds, pa, geo.p,
-                               live.p, queue.p, hits.p, overflow.p, ctr.p, nullptr);
-        HIPCHK(hipGetLastError());
-        std::vector<float2> h((size_t)n);
-        HIPCHK(hipMemcpyAsync(h.data(), hits.p, (size_t)n * sizeof(float2), hipMemcpyDeviceToHost, s0));
-        HIPCHK(hipStreamSynchronize(s0));
-        for (int i = 0; i < n; i++) {
-            if (t_out) t_out[i] = h[i].x;
-            if (index_out) std::memcpy(&index_out[i], &h[i].y, 4);
-        }
-        if (st) {
-            std::memset(st, 0, sizeof(*st));
-            std::vector<Counters> slots(kCtrSlots);
-            HIPCHK(hipMemcpy(slots.data(), ctr.p, sizeof(Counters) * kCtrSlots, hipMemcpyDeviceToHost));
-            for (const Counters &x : slots) {
-                st->live_segments += x.live; st->nodes_popped += x.pn; st->internal_visits += x.iv;
-                st->triangle_tests += x.tt; st->sphere_tests += x.st;
-            }
-        }
         return RT_OK;
     }
 
@@ -2516,7 +1930,7 @@ struct rt_renderer {
     int run_impl(int pass_begin, int count, int stride, float *pass_sums, rt_stats *st, size_t pitch, bool async) {
         const auto w0 = std::chrono::high_resolution_clock::now();
         enqueued = false;
-        HIPCHK(hipSetDevice(device));
+        HIPCHK(hipSetDevice(scene.device));
         if (stride < 1) stride = 1;
         const int P = pass_count();
         if (count < 0) count = pass_begin < P ? (P - pass_begin + stride - 1) / stride : 0;
@@ -2539,8 +1953,8 @@ struct rt_renderer {
         if (pass_events && tspans.n < (size_t)std::max(count, 1) * kSpanWords * (bounces + 1)) {
             if (int rc = tspans.alloc((size_t)std::max(count, 1) * kSpanWords * (bounces + 1))) return rc;
         }
-        if (!wall_khz) HIPCHK(hipDeviceGetAttribute(&wall_khz, hipDeviceAttributeWallClockRate, device));
-        HIPCHK(hipMemsetAsync(ctr.p, 0, sizeof(Counters) * kCtrSlots, s0));
+        if (!wall_khz) HIPCHK(hipDeviceGetAttribute(&wall_khz, hipDeviceAttributeWallClockRate, scene.device));
+        HIPCHK(hipMemsetAsync(scene.ctr.p, 0, sizeof(Counters) * kCtrSlots, s0));
         HIPCHK(hipEventRecord(t_begin, s0));
         for (int k = 1; k < inflight; k++) HIPCHK(hipStreamWaitEvent(ctx[k].stream, t_begin, 0));
         for (auto &c : ctx) c.ev = 0;
@@ -2698,7 +2112,7 @@ struct rt_renderer {
     int finish_run(rt_stats *st) {
         if (!run_pending) return rtamd::fail(RT_E_INVALID, "rt_renderer_finish: no run in flight");
         run_pending = false;
-        HIPCHK(hipSetDevice(device));
+        HIPCHK(hipSetDevice(scene.device));
         const int count = run_count, inflight = run_inflight;
         const bool events = run_events, tsorted = run_tsort, inl = run_inline;
         const int64_t sorted = run_sorted, generated = run_generated;
@@ -2726,13 +2140,8 @@ struct rt_renderer {
 #endif
         if (st) {
             std::memset(st, 0, sizeof(*st));
-            std::vector<Counters> slots(kCtrSlots);
-            HIPCHK(hipMemcpy(slots.data(), ctr.p, sizeof(Counters) * kCtrSlots, hipMemcpyDeviceToHost));
             Counters c{};
-            for (const Counters &x : slots) {
-                c.live += x.live; c.pn += x.pn; c.iv += x.iv; c.tt += x.tt; c.st += x.st;
-                c.hits += x.hits; c.misses += x.misses; c.hits_sphere += x.hits_sphere;
-            }
+            if (int rc = scene.read_counters(c)) return rc;
             float ms = 0;
             HIPCHK(hipEventElapsedTime(&ms, t_begin, t_end));
             st->kernel_ms = ms;
@@ -2827,19 +2236,6 @@ struct rt_renderer {
 
 namespace {
 
-int check_scene(const rt_scene *s) {
-    if (!s) return rtamd::fail(RT_E_INVALID, "null scene");
-    if (s->width < 2 || s->height < 2 || s->ray_count < 0 || s->bounces < 0)
-        return rtamd::fail(RT_E_INVALID, "scene image must be at least 2x2 with non-negative spp/bounces");
-    if (s->bvh_node_count < 1 || !s->bvh) return rtamd::fail(RT_E_INVALID, "scene has no BVH root");
-    if (s->environment_map_width < 1 || s->environment_map_height < 1 || !s->environment_map)
-        return rtamd::fail(RT_E_INVALID, "scene has no environment map");
-    if ((s->sphere_count && !s->spheres) || (s->triangle_count && !s->triangles) || !s->materials ||
-        (s->sphere_count + s->triangle_count && !s->material_indices))
-        return rtamd::fail(RT_E_INVALID, "scene array missing");
-    return RT_OK;
-}
-
 int run_bloom(float *d_fb, int w, int h, float threshold, int radius, hipStream_t s) {
     const int pixels = w * h;
     float *bright = nullptr, *blur = nullptr;
@@ -2860,224 +2256,6 @@ int run_bloom(float *d_fb, int w, int h, float threshold, int radius, hipStream_
 }
 
 }  // namespace
-
-// Resident ray queries (rt_query_*): a scene-only renderer (no pass contexts) plus the scratch of one
-// call -- the repacked rays, trace_kernel's {t, index} records, the live count and queue words, the
-// overflow stacks -- kept between calls.  The device-pointer calls enqueue on the caller's stream and,
-// once the scratch holds n rays, allocate nothing and never wait on the host.  Calls share the scratch,
-// so each records `last` and the next call's stream waits for it; a regrow waits for it on the host
-// before the old scratch is freed.
-struct rt_query {
-    rt_renderer r;
-    int blocks = 0;                   // most workgroups either traversal kernel keeps resident
-    size_t cap = 0;                   // rays the scratch holds
-    DevBuf<float4> geo;
-    DevBuf<float2> hits;
-    DevBuf<uint32_t> words, overflow; // words: live count, then the queue shards
-    // staging of the host-pointer calls
-    size_t host_cap = 0;
-    DevBuf<float> s_rays, s_tmax, s_t;
-    DevBuf<int32_t> s_index;
-    DevBuf<uint8_t> s_occ;
-    hipEvent_t last = nullptr;
-    bool pending = false;             // `last` has been recorded
-    int last_kind = 0;                // 0 none (or an update), 1 closest, 2 occluded
-    int32_t last_n = 0;
-    rtamd::RefitPlan plan;            // rt_query_update_triangles: level tables, built in init
-
-    ~rt_query() {
-        (void)hipSetDevice(r.device);
-        if (last) {
-            if (pending) (void)hipEventSynchronize(last);
-            (void)hipEventDestroy(last);
-        }
-    }
-    uint32_t *live() const { return words.p; }
-    uint32_t *queue() const { return words.p + kQueueStride; }
-
-    int init(const rt_scene *sc, const rt_opts *o) {
-        int rc = r.init(sc, o, false);
-        if (rc) return rc;
-        int per_cu_c = 0, per_cu_a = 0;
-        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_c, trace_kernel<false, false, false>, kBlock, 0));
-        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_a, anyhit_kernel<false>, kBlock, 0));
-        blocks = std::max(1, r.cus * std::max({1, per_cu_c, per_cu_a}));
-        HIPCHK(hipEventCreateWithFlags(&last, hipEventDisableTiming));
-        if ((rc = words.alloc((size_t)(1 + kQueues) * kQueueStride))) return rc;
-        if ((rc = plan.build(sc, r.node_rec, r.stream()))) return rc;
-        // trace_kernel: 2 words (ref, distance) for each of kStackMax - kStackLds entries per lane; the
-        // any-hit kernel's kStackMax - kAnyStackLds one-word entries fit in the same buffer
-        return overflow.alloc((size_t)blocks * kBlock * 2 * (kStackMax - kStackLds));
-    }
-    int wait_last() {
-        if (pending) HIPCHK(hipEventSynchronize(last));
-        return RT_OK;
-    }
-    int reserve(int64_t n) {
-        if ((size_t)n <= cap) return RT_OK;
-        HIPCHK(hipSetDevice(r.device));
-        int rc = wait_last();           // the last call may still read the old scratch
-        if (rc) return rc;
-        const size_t want = std::max<size_t>({(size_t)n, 2 * cap, (size_t)kBlock});
-        cap = 0;
-        if ((rc = geo.alloc(want * 2)) || (rc = hits.alloc(want))) return rc;
-        cap = want;
-        return RT_OK;
-    }
-    int begin(const float *d_rays, const float *d_tmax, int n, hipStream_t s) {
-        HIPCHK(hipSetDevice(r.device));
-        int rc = reserve(n);
-        if (rc) return rc;
-        if (pending) HIPCHK(hipStreamWaitEvent(s, last, 0));
-        hipLaunchKernelGGL(query_ingest_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, s, d_rays, d_tmax, (uint32_t)n, geo.p,
-                           live(), queue(), r.ctr.p);
-        return RT_OK;
-    }
-    int end(int kind, int n, hipStream_t s) {
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(last, s));
-        pending = true;
-        last_kind = kind;
-        last_n = n;
-        return RT_OK;
-    }
-    int closest(const float *d_rays, int n, float *d_t, int32_t *d_index, hipStream_t s) {
-        int rc = begin(d_rays, nullptr, n, s);
-        if (rc) return rc;
-        const PassArgs pa{1, 0u, FastDiv::of(1), FastDiv::of((uint32_t)r.width), SlotMap::identity()};
-        const int grid = std::min(blocks_for(n), blocks);
-        if (r.counters)
-            hipLaunchKernelGGL((trace_kernel<false, true, false>), dim3(grid), dim3(kBlock), 0, s, r.ds, pa, geo.p, live(),
-                               queue(), hits.p, overflow.p, r.ctr.p, nullptr);
-        else
-            hipLaunchKernelGGL((trace_kernel<false, false, false>), dim3(grid), dim3(kBlock), 0, s, r.ds, pa, geo.p, live(),
-                               queue(), hits.p, overflow.p, r.ctr.p, nullptr);
-        hipLaunchKernelGGL(query_egest_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, s, hits.p, (uint32_t)n, d_t, d_index,
-                           r.ds.sphere_count, r.ctr.p);
-        return end(1, n, s);
-    }
-    int occluded(const float *d_rays, const float *d_tmax, int n, uint8_t *d_occ, hipStream_t s) {
-        int rc = begin(d_rays, d_tmax, n, s);
-        if (rc) return rc;
-        const int grid = std::min(blocks_for(n), blocks);
-        if (r.counters)
-            hipLaunchKernelGGL(anyhit_kernel<true>, dim3(grid), dim3(kBlock), 0, s, r.ds, geo.p, live(), queue(), d_occ,
-                               overflow.p, r.ctr.p);
-        else
-            hipLaunchKernelGGL(anyhit_kernel<false>, dim3(grid), dim3(kBlock), 0, s, r.ds, geo.p, live(), queue(), d_occ,
-                               overflow.p, r.ctr.p);
-        return end(2, n, s);
-    }
-    int reserve_host(int n) {
-        if ((size_t)n <= host_cap) return RT_OK;
-        HIPCHK(hipSetDevice(r.device));
-        const size_t want = std::max<size_t>({(size_t)n, 2 * host_cap, (size_t)kBlock});
-        host_cap = 0;                   // the host calls are blocking: nothing reads the old staging
-        int rc;
-        if ((rc = s_rays.alloc(want * 6)) || (rc = s_tmax.alloc(want)) || (rc = s_t.alloc(want)) ||
-            (rc = s_index.alloc(want)) || (rc = s_occ.alloc(want)))
-            return rc;
-        host_cap = want;
-        return RT_OK;
-    }
-    int closest_host(const float *rays, int n, float *t, int32_t *index) {
-        int rc = reserve_host(n);
-        if (rc) return rc;
-        hipStream_t s = r.stream();
-        HIPCHK(hipMemcpyAsync(s_rays.p, rays, (size_t)n * 6 * sizeof(float), hipMemcpyHostToDevice, s));
-        if ((rc = closest(s_rays.p, n, s_t.p, s_index.p, s))) return rc;
-        HIPCHK(hipMemcpyAsync(t, s_t.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(index, s_index.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        return RT_OK;
-    }
-    int occluded_host(const float *rays, const float *tmax, int n, uint8_t *occ) {
-        int rc = reserve_host(n);
-        if (rc) return rc;
-        hipStream_t s = r.stream();
-        HIPCHK(hipMemcpyAsync(s_rays.p, rays, (size_t)n * 6 * sizeof(float), hipMemcpyHostToDevice, s));
-        if (tmax) HIPCHK(hipMemcpyAsync(s_tmax.p, tmax, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s));
-        if ((rc = occluded(s_rays.p, tmax ? s_tmax.p : nullptr, n, s_occ.p, s))) return rc;
-        HIPCHK(hipMemcpyAsync(occ, s_occ.p, (size_t)n, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        return RT_OK;
-    }
-    // New vertices under the frozen topology.  An update overwrites what a query reads, so
-    // it joins the `last` chain like a query: queries enqueued later, on any stream, see the new geometry.
-    int update(const float *d_vertices, hipStream_t s) {
-        HIPCHK(hipSetDevice(r.device));
-        if (pending) HIPCHK(hipStreamWaitEvent(s, last, 0));
-        int rc = plan.enqueue(d_vertices, r.tris.p, r.nodes.p, r.big.p, s);
-        if (rc) return rc;
-        return end(0, 0, s);
-    }
-    int update_host(const float *vertices) {
-        HIPCHK(hipSetDevice(r.device));
-        const size_t count = (size_t)plan.triangle_count * 9;
-        if (!plan.d_stage) HIPCHK(hipMalloc(reinterpret_cast<void **>(&plan.d_stage), count * sizeof(float)));
-        hipStream_t s = r.stream();
-        HIPCHK(hipMemcpyAsync(plan.d_stage, vertices, count * sizeof(float), hipMemcpyHostToDevice, s));
-        int rc = update(plan.d_stage, s);
-        if (rc) return rc;
-        HIPCHK(hipStreamSynchronize(s));
-        return RT_OK;
-    }
-    // The device's current triangles and the node array in the scene's numbering (inspection, tests).
-    int read_geometry(rt_triangle *tris_out, rt_bvh_node *bvh_out) {
-        HIPCHK(hipSetDevice(r.device));
-        int rc = wait_last();
-        if (rc) return rc;
-        if (tris_out && plan.triangle_count)
-            HIPCHK(hipMemcpy(tris_out, r.tris.p, (size_t)plan.triangle_count * sizeof(rt_triangle), hipMemcpyDeviceToHost));
-        if (!bvh_out) return RT_OK;
-        using rtamd::refit::Box;
-        std::copy(plan.bvh.begin(), plan.bvh.end(), bvh_out);
-        if (plan.root_leaf) {
-            float4 box[2];
-            HIPCHK(hipMemcpy(box, plan.d_root_box, sizeof(box), hipMemcpyDeviceToHost));
-            bvh_out[0].min_bound = {box[0].x, box[0].y, box[0].z};
-            bvh_out[0].max_bound = {box[1].x, box[1].y, box[1].z};
-            return RT_OK;
-        }
-        std::vector<float4> rec_h(plan.rec_node.size() * 4);
-        HIPCHK(hipMemcpy(rec_h.data(), r.nodes.p, rec_h.size() * sizeof(float4), hipMemcpyDeviceToHost));
-        for (size_t k = 0; k < plan.rec_node.size(); k++) {
-            const int i = plan.rec_node[k];
-            if (i < 0) continue;
-            const float4 *q = &rec_h[k * 4];
-            rt_bvh_node &l = bvh_out[plan.bvh[i].child1], &rr = bvh_out[plan.bvh[i].child2];
-            l.min_bound = {q[0].x, q[0].z, q[1].x};
-            l.max_bound = {q[1].z, q[2].x, q[2].z};
-            rr.min_bound = {q[0].y, q[0].w, q[1].y};
-            rr.max_bound = {q[1].w, q[2].y, q[2].w};
-            if (i == 0) {                   // the root's own box: the merge of its record
-                Box b = rtamd::refit::empty_box();
-                rtamd::refit::grow(b, Box{l.min_bound, l.max_bound});
-                rtamd::refit::grow(b, Box{rr.min_bound, rr.max_bound});
-                bvh_out[0].min_bound = b.lo;
-                bvh_out[0].max_bound = b.hi;
-            }
-        }
-        return RT_OK;
-    }
-    int stats(rt_stats *st) {
-        std::memset(st, 0, sizeof(*st));
-        if (!pending) return RT_OK;
-        HIPCHK(hipSetDevice(r.device));
-        int rc = wait_last();
-        if (rc) return rc;
-        if (last_kind == 0) return RT_OK;   // an update since the last query: nothing was traced
-        std::vector<Counters> slots(kCtrSlots);
-        HIPCHK(hipMemcpy(slots.data(), r.ctr.p, sizeof(Counters) * kCtrSlots, hipMemcpyDeviceToHost));
-        for (const Counters &x : slots) {
-            st->nodes_popped += x.pn; st->internal_visits += x.iv; st->triangle_tests += x.tt;
-            st->sphere_tests += x.st; st->hits += x.hits; st->hits_sphere += x.hits_sphere;
-        }
-        st->live_segments = (uint64_t)last_n;
-        st->misses = st->live_segments - st->hits;
-        return RT_OK;
-    }
-};
 
 extern "C" {
 
@@ -3122,11 +2300,9 @@ int create_renderer(const rt_scene *scene, const rt_opts *opts, rt_renderer **ou
                     int inflight_limit = 0) {
     if (!out) return rtamd::fail(RT_E_INVALID, "null output");
     *out = nullptr;
-    int rc = check_scene(scene);
-    if (rc) return rc;
     rt_opts o;
-    if (opts) o = *opts; else rt_default_opts(&o);
-    if (rt_device_count() <= o.device || o.device < 0) return rtamd::fail(RT_E_NODEVICE, "no such HIP device");
+    int rc = resolve_opts(scene, opts, o);
+    if (rc) return rc;
     auto *r = new rt_renderer();
     r->pass_hint = pass_hint;
     r->inflight_limit = inflight_limit;
@@ -3169,7 +2345,7 @@ int rt_renderer_run_host(rt_renderer *r, int32_t pass_begin, int32_t count, int3
                          rt_stats *stats) {
     if (!r || !host_pass_sums || count < 1) return rtamd::fail(RT_E_INVALID, "rt_renderer_run_host: bad argument");
     if (int rc = r->busy("rt_renderer_run_host")) return rc;
-    HIPCHK(hipSetDevice(r->device));
+    HIPCHK(hipSetDevice(r->scene.device));
     const size_t bytes = (size_t)count * r->width * r->height * 3 * sizeof(float);
     float *d = nullptr;
     HIPCHK(hipMalloc(reinterpret_cast<void **>(&d), bytes));
@@ -3185,7 +2361,7 @@ int rt_renderer_run_host(rt_renderer *r, int32_t pass_begin, int32_t count, int3
 int rt_renderer_read_framebuffer(rt_renderer *r, float *fb_out) {
     if (!r || !fb_out) return rtamd::fail(RT_E_INVALID, "null argument");
     if (int rc = r->busy("rt_renderer_read_framebuffer")) return rc;
-    HIPCHK(hipSetDevice(r->device));
+    HIPCHK(hipSetDevice(r->scene.device));
     HIPCHK(hipMemcpyAsync(fb_out, r->fb.p, r->fb.n * sizeof(float), hipMemcpyDeviceToHost, r->stream()));
     HIPCHK(hipStreamSynchronize(r->stream()));
     return RT_OK;
@@ -3194,7 +2370,7 @@ int rt_renderer_read_framebuffer(rt_renderer *r, float *fb_out) {
 int rt_renderer_copy_framebuffer(rt_renderer *r, float *d_out) {
     if (!r || !d_out) return rtamd::fail(RT_E_INVALID, "null argument");
     if (int rc = r->busy("rt_renderer_copy_framebuffer")) return rc;
-    HIPCHK(hipSetDevice(r->device));
+    HIPCHK(hipSetDevice(r->scene.device));
     HIPCHK(hipMemcpyAsync(d_out, r->fb.p, r->fb.n * sizeof(float), hipMemcpyDeviceToDevice, r->stream()));
     HIPCHK(hipStreamSynchronize(r->stream()));
     return RT_OK;
@@ -3203,7 +2379,7 @@ int rt_renderer_copy_framebuffer(rt_renderer *r, float *d_out) {
 int rt_renderer_clear(rt_renderer *r) {
     if (!r) return rtamd::fail(RT_E_INVALID, "null renderer");
     if (int rc = r->busy("rt_renderer_clear")) return rc;
-    HIPCHK(hipSetDevice(r->device));
+    HIPCHK(hipSetDevice(r->scene.device));
     HIPCHK(hipMemsetAsync(r->fb.p, 0, r->fb.n * sizeof(float), r->stream()));
     HIPCHK(hipStreamSynchronize(r->stream()));
     return RT_OK;
@@ -3225,7 +2401,7 @@ int rt_renderer_wait_pass(rt_renderer *r, int32_t k, void *hip_stream) {
     if (!r) return rtamd::fail(RT_E_INVALID, "null renderer");
     if (!r->run_pending || k < 0 || k >= r->run_count || k >= (int)r->pass_done.size())
         return rtamd::fail(RT_E_INVALID, "rt_renderer_wait_pass: no such pass in the async run");
-    HIPCHK(hipSetDevice(r->device));
+    HIPCHK(hipSetDevice(r->scene.device));
     HIPCHK(hipStreamWaitEvent(static_cast<hipStream_t>(hip_stream), r->pass_done[k], 0));
     return RT_OK;
 }
@@ -3255,7 +2431,7 @@ int rt_renderer_set_exchange(rt_renderer *r, rt_exchange_fn fn, void *user, int3
     r->xuser = user;
     r->x_on_device = on_device != 0;
     if (fn && !r->x_on_device && !r->xhost && r->tsort()) {
-        HIPCHK(hipSetDevice(r->device));
+        HIPCHK(hipSetDevice(r->scene.device));
         const size_t n = (size_t)r->width * r->height * std::min(20, std::max(1, r->spp));
         HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&r->xhost), n));
     }
@@ -3286,7 +2462,7 @@ int rt_renderer_set_exchange_rccl(rt_renderer *r, const uint8_t *id, int32_t nra
     if (!r || !id || nranks < 1 || rank < 0 || rank >= nranks)
         return rtamd::fail(RT_E_INVALID, "rt_renderer_set_exchange_rccl: bad argument");
     if (r->xcomm) return rtamd::fail(RT_E_INVALID, "rt_renderer_set_exchange_rccl: the renderer already has a communicator");
-    HIPCHK(hipSetDevice(r->device));
+    HIPCHK(hipSetDevice(r->scene.device));
     ncclUniqueId uid;
     std::memcpy(&uid, id, sizeof(uid));
     ncclComm_t comm = nullptr;
@@ -3358,109 +2534,6 @@ int rt_render(const rt_scene *scene, const rt_opts *opts, float *fb_out, rt_stat
     if (!rc && stats) stats->render_ms = ms_since(w0);
     return rc;
 }
-
-int rt_trace_rays(const rt_scene *scene, const rt_opts *opts, const float *rays, int32_t n, float *t_out,
-                  int32_t *index_out, rt_stats *stats) {
-    if (n < 0 || (n > 0 && !rays)) return rtamd::fail(RT_E_INVALID, "rt_trace_rays: bad argument");
-    int rc = check_scene(scene);
-    if (rc) return rc;
-    rt_opts o;
-    if (opts) o = *opts; else rt_default_opts(&o);
-    if (rt_device_count() <= o.device || o.device < 0) return rtamd::fail(RT_E_NODEVICE, "no such HIP device");
-    auto *r = new rt_renderer();
-    rc = r->init(scene, &o, false);
-    if (!rc) rc = r->trace_rays(rays, n, t_out, index_out, stats);
-    delete r;
-    return rc;
-}
-
-int rt_query_create(const rt_scene *scene, const rt_opts *opts, rt_query **out) {
-    if (!out) return rtamd::fail(RT_E_INVALID, "rt_query_create: null output");
-    *out = nullptr;
-    int rc = check_scene(scene);
-    if (rc) return rc;
-    rt_opts o;
-    if (opts) o = *opts; else rt_default_opts(&o);
-    if (rt_device_count() <= o.device || o.device < 0) return rtamd::fail(RT_E_NODEVICE, "no such HIP device");
-    auto *q = new rt_query();
-    rc = q->init(scene, &o);
-    if (rc) { delete q; return rc; }
-    *out = q;
-    return RT_OK;
-}
-
-int rt_query_reserve(rt_query *q, int32_t n) {
-    if (!q) return rtamd::fail(RT_E_INVALID, "rt_query_reserve: null query object");
-    if (n < 0) return rtamd::fail(RT_E_INVALID, "rt_query_reserve: negative ray count");
-    return q->reserve(n);
-}
-
-int rt_query_closest(rt_query *q, const float *d_rays, int32_t n, float *d_t, int32_t *d_index, void *hip_stream) {
-    if (!q) return rtamd::fail(RT_E_INVALID, "rt_query_closest: null query object");
-    if (n < 0) return rtamd::fail(RT_E_INVALID, "rt_query_closest: negative ray count");
-    if (n == 0) return RT_OK;
-    if (!d_rays || !d_t || !d_index) return rtamd::fail(RT_E_INVALID, "rt_query_closest: null pointer");
-    return q->closest(d_rays, n, d_t, d_index, static_cast<hipStream_t>(hip_stream));
-}
-
-int rt_query_occluded(rt_query *q, const float *d_rays, const float *d_tmax, int32_t n, uint8_t *d_occluded,
-                      void *hip_stream) {
-    if (!q) return rtamd::fail(RT_E_INVALID, "rt_query_occluded: null query object");
-    if (n < 0) return rtamd::fail(RT_E_INVALID, "rt_query_occluded: negative ray count");
-    if (n == 0) return RT_OK;
-    if (!d_rays || !d_occluded) return rtamd::fail(RT_E_INVALID, "rt_query_occluded: null pointer");
-    return q->occluded(d_rays, d_tmax, n, d_occluded, static_cast<hipStream_t>(hip_stream));
-}
-
-int rt_query_closest_host(rt_query *q, const float *rays, int32_t n, float *t, int32_t *index) {
-    if (!q) return rtamd::fail(RT_E_INVALID, "rt_query_closest_host: null query object");
-    if (n < 0) return rtamd::fail(RT_E_INVALID, "rt_query_closest_host: negative ray count");
-    if (n == 0) return RT_OK;
-    if (!rays || !t || !index) return rtamd::fail(RT_E_INVALID, "rt_query_closest_host: null pointer");
-    return q->closest_host(rays, n, t, index);
-}
-
-int rt_query_occluded_host(rt_query *q, const float *rays, const float *tmax, int32_t n, uint8_t *occluded) {
-    if (!q) return rtamd::fail(RT_E_INVALID, "rt_query_occluded_host: null query object");
-    if (n < 0) return rtamd::fail(RT_E_INVALID, "rt_query_occluded_host: negative ray count");
-    if (n == 0) return RT_OK;
-    if (!rays || !occluded) return rtamd::fail(RT_E_INVALID, "rt_query_occluded_host: null pointer");
-    return q->occluded_host(rays, tmax, n, occluded);
-}
-
-int rt_query_stats(rt_query *q, rt_stats *stats) {
-    if (!q || !stats) return rtamd::fail(RT_E_INVALID, "rt_query_stats: null argument");
-    return q->stats(stats);
-}
-
-static_assert(rtamd::kRefLeaf == kLeaf && rtamd::kRefBigLeaf == kBigLeaf, "bvh_refit.hip reads the records' leaf refs");
-
-int rt_query_update_triangles(rt_query *q, const float *d_vertices, int32_t triangle_count, void *hip_stream) {
-    if (!q) return rtamd::fail(RT_E_INVALID, "rt_query_update_triangles: null query object");
-    if (triangle_count != q->plan.triangle_count)
-        return rtamd::fail(RT_E_INVALID, "rt_query_update_triangles: triangle_count " + std::to_string(triangle_count) +
-                                             " is not the scene's " + std::to_string(q->plan.triangle_count));
-    if (triangle_count == 0) return RT_OK;
-    if (!d_vertices) return rtamd::fail(RT_E_INVALID, "rt_query_update_triangles: null pointer");
-    return q->update(d_vertices, static_cast<hipStream_t>(hip_stream));
-}
-
-int rt_query_update_triangles_host(rt_query *q, const float *vertices, int32_t triangle_count) {
-    if (!q) return rtamd::fail(RT_E_INVALID, "rt_query_update_triangles_host: null query object");
-    if (triangle_count != q->plan.triangle_count)
-        return rtamd::fail(RT_E_INVALID, "rt_query_update_triangles_host: triangle_count " + std::to_string(triangle_count) +
-                                             " is not the scene's " + std::to_string(q->plan.triangle_count));
-    if (triangle_count == 0) return RT_OK;
-    if (!vertices) return rtamd::fail(RT_E_INVALID, "rt_query_update_triangles_host: null pointer");
-    return q->update_host(vertices);
-}
-
-int rt_query_read_geometry(rt_query *q, rt_triangle *triangles_out, rt_bvh_node *bvh_out) {
-    if (!q) return rtamd::fail(RT_E_INVALID, "rt_query_read_geometry: null query object");
-    return q->read_geometry(triangles_out, bvh_out);
-}
-
-void rt_query_destroy(rt_query *q) { delete q; }
 
 int rt_bloom_device(float *d_fb, int32_t w, int32_t h, float threshold, int32_t radius, int32_t device) {
     if (!d_fb || w <= 0 || h <= 0 || radius < 0) return rtamd::fail(RT_E_INVALID, "rt_bloom_device: bad argument");

@@ -271,12 +271,13 @@ void rt_multi_destroy(rt_multi *m);
  * (scene.cu:134-241) -- one bounce of process_ray up to the hit (scene.cu:320-374) -- through
  * the render's traversal kernel.  t_out[i] = closest distance (1e30 when nothing is hit),
  * index_out[i] = primitive index (spheres first, then sphere_count + triangle; -1 = miss).
- * With opts->collect_counters the traversal counters are returned in stats. */
+ * With opts->collect_counters the traversal counters are returned in stats.  One call is
+ * rt_query_create + rt_query_closest_host + rt_query_destroy; t_out, index_out and stats may be NULL. */
 int rt_trace_rays(const rt_scene *scene, const rt_opts *opts, const float *rays, int32_t n,
                   float *t_out, int32_t *index_out, rt_stats *stats);
 
-/* Resident ray queries: the scene and BVH stay in HBM (a scene-only renderer: no pass contexts, so the
- * object costs the scene plus its scratch) and device pointers go in and out on the caller's stream.
+/* Resident ray queries: the scene and BVH stay in HBM (the object costs the scene plus its scratch: no
+ * framebuffer, no pass contexts) and device pointers go in and out on the caller's stream.
  * The presence of these symbols is the feature probe; RT_ABI_VERSION, rt_opts and rt_stats are unchanged.
  * No reference counterpart as an interface (the reference traced only its own render's rays); what each
  * call computes restates the reference's traversal:

@@ -86,6 +86,18 @@ int main(int argc, char **argv) {
     if (!f || std::fwrite(fb.data(), sizeof(float), fb.size(), f) != fb.size()) return 1;
     std::fclose(f);
     std::printf("{\"pass0\": true, \"live_segments\": %llu}\n", (unsigned long long)st.live_segments);
+    // rt_trace_rays: each output is optional (the camera's ray down the view axis, twice)
+    {
+        const float ray[6] = {s->camera_position.x, s->camera_position.y, s->camera_position.z, 0.0f, 0.0f, -1.0f};
+        float t = 0;
+        int32_t index = 0;
+        rt_stats ts;
+        if (rt_trace_rays(s, nullptr, ray, 1, &t, nullptr, &ts) || rt_trace_rays(s, nullptr, ray, 1, &t, &index, nullptr)) {
+            std::printf("Error rt_trace_rays %s\n", rt_last_error());
+            return 1;
+        }
+        std::printf("{\"trace_rays_null_outputs\": true, \"live_segments\": %llu}\n", (unsigned long long)ts.live_segments);
+    }
     rt_scene_free(h);
     return 0;
 }

@@ -31,6 +31,8 @@ def test_cpp_host_default_environment(tmp_path):
     assert len(runs) == 2 and all(r["passes"] == 20 and r["gpu_max_hw_queues"] == "24" for r in runs)
     # 20 passes of 41.5 M rays x 16 bounces: the default-queue cliff is ~11 ms/pass, the benchmark ~5.9
     assert runs[-1]["ms_per_pass"] < 8.0, runs
+    # rt_trace_rays with index_out == nullptr and with stats == nullptr both returned RT_OK
+    assert [x for x in lines if "trace_rays_null_outputs" in x] == [{"trace_rays_null_outputs": True, "live_segments": 1}]
     fb = np.fromfile(fb_path, dtype="<f4")
     assert fb.size == 1920 * 1080 * 3
     assert hashlib.sha256(fb.tobytes()).hexdigest() == gold["sha256"]

@@ -99,6 +99,27 @@ def test_trace_rays_bitexact(scene, use_bvh):
         assert name in ("non_finite", "outward") or (i_o >= 0).any()
 
 
+def test_trace_rays_pinned():
+    """rt_trace_rays on 257 stored rays (one full workgroup and one lane of the next) against what the
+    library returned before rt_trace_rays became a temporary rt_query (tests/golden/trace_rays_pin.npz,
+    recorded by tests/golden/make_trace_rays_pin.py on that revision): t and index bit for bit and every
+    rt_stats field, with the work counters on and off.  In particular live_segments is the kernel's own
+    count of rays taken from its queue, and hits, misses and hits_sphere stay 0."""
+    import json
+    import os
+    pin = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "trace_rays_pin.npz"))
+    rays = pin["rays"]
+    assert rays.shape == (257, 6)
+    dev = R.Scene("%s/cornell.scene" % R.ASSETS, image=(16, 16, 1, 1))
+    for name, on in (("on", True), ("off", False)):
+        t, idx, st = R.trace_rays(dev, rays, counters=on)
+        assert np.array_equal(t.view(np.uint32), pin["t_" + name]), name
+        assert np.array_equal(idx, pin["index_" + name]), name
+        want = json.loads(str(pin["stats_" + name]))
+        assert st == want, (name, {k: (st[k], want[k]) for k in want if st.get(k) != want[k]})
+    assert json.loads(str(pin["stats_on"]))["nodes_popped"] > 0      # the fixture's counters were on
+
+
 def test_trace_rays_empty_and_single():
     orc, dev = _scenes("cornell")
     t, i, _ = R.trace_rays(dev, np.zeros((0, 6), np.float32))

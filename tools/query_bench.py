@@ -7,8 +7,8 @@ triangle normal (turned towards the incoming ray), drawn from a seeded torch gen
 warm-up, `--calls` times each in alternation (one call of every leg per round, the order within a round shuffled from the seed):
 
   closest_device    RayQuery.closest on the device tensors (resident scene, caller's stream)
-  trace_rays_host   the one-shot rt_trace_rays on the same rays through host memory (scene uploaded, rays
-                    repacked on the host, scratch allocated and freed, results copied back: per call)
+  trace_rays_host   the one-shot rt_trace_rays on the same rays through host memory (a query object created,
+                    scene uploaded, scratch allocated and freed, results copied back: per call)
   occluded_tmax     RayQuery.occluded on the hemisphere rays, tmax = 10 % of the scene diagonal
   occluded_any      the same rays, tmax = None
   closest_hemi      RayQuery.closest on the hemisphere rays (the closest-hit cost of the same rays)
