@@ -78,6 +78,11 @@ __global__ __launch_bounds__(kBlock) void query_egest_kernel(const float2 *__res
 // with a non-finite 1/d are trace_kernel's.  out[slot] = 0 or 1, stored at refill and at exit like hits[].
 // Counters (COUNT): Pn = nodes entered, Iv = internal nodes stepped, Tt = triangle tests, sphere tests up
 // to the first accepted sphere -- the oracle's numbers on unoccluded rays, order-dependent on occluded ones.
+// The order is a function of (ray, B, tree) alone: spheres in order; the root; at an internal node child 1
+// (the record's second) goes first iff it is entered and child 0 is not or t1 < t0 (a tie goes to child 0),
+// the other one is pushed iff both are entered; a leaf's triangles in order; an exhausted leaf, or a node
+// with no entered child, pops.  tests/anyhit_ref.py (AnyHitOrderRef) restates it and
+// tests/test_gpu_anyhit_order.py pins the counters to it on all rays, occluded ones included.
 constexpr int kAnyStackLds = 16;
 
 template <bool COUNT>

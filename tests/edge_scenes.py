@@ -15,6 +15,8 @@
 import math
 import os
 
+import numpy as np
+
 
 def _tri(p, q, r):
     return "triangle white %s %s %s\n" % tuple(" ".join("%.9g" % c for c in v) for v in (p, q, r))
@@ -50,6 +52,90 @@ def deep_scene():
     s += "camera position 1e29 0.05 0.05 forward -1 0 0 up 0 1 0 fov 2\n"
     s += "image 32 32 20 3 1\n"
     return s
+
+
+# ---------------------------------------------------------------- ray sets for deep.scene
+# Every triangle of deep has the yz projection (-1, 1.2), (1, 1), (1.2, -1): (0.4, 0.4) lies inside it, the
+# x axis runs through the gap it leaves.  The *_plus sets run toward +x, the direction in which the any-hit
+# kernel (near child first, far child pushed) stacks one entry per level; the *_minus sets run toward -x,
+# the direction in which the reference's order (trace_kernel) does.  All are seeded: the same (n, seed)
+# gives the same floats.
+
+def _unit(v):
+    v = np.asarray(v, np.float32)
+    return (v / np.sqrt((v * v).sum(-1, keepdims=True)).astype(np.float32)).astype(np.float32)
+
+
+def _gap_yz(n, rng):
+    return (rng.random((n, 2)) * 0.2 - 0.1).astype(np.float32)       # inside every triangle's gap
+
+
+def _rays(o, d):
+    return np.ascontiguousarray(np.hstack([o, d]), np.float32)
+
+
+def axis_plus(n, seed=21):
+    """From x = -5 along +x through the gap: the whole chain is walked, nothing is hit."""
+    rng = np.random.default_rng(seed)
+    o = np.hstack([np.full((n, 1), -5.0, np.float32), _gap_yz(n, rng)])
+    return _rays(o, np.tile(np.array([[1, 0, 0]], np.float32), (n, 1)))
+
+
+def solid_plus(n, seed=21):
+    """axis_plus shifted by +0.5 in y and z, into the triangles: stopped by triangle 0, which the any-hit
+    kernel reaches in the bottom leaf with one pushed node per level above it still on the stack."""
+    r = axis_plus(n, seed)
+    r[:, 1:3] += np.float32(0.5)
+    return r
+
+
+def tilted_plus(n, seed=22):
+    """From (0.5, y, z) in the gap along normalize(1, 1.3 * 3^-k, 0), k uniform in [5, 59): the ray leaves the
+    triangles' common yz box near x = 3^k, so only the levels below that point push, and it is stopped on the
+    way out (where y is in 0.2 .. 1.1 at a triangle's x), after pops."""
+    rng = np.random.default_rng(seed)
+    o = np.hstack([np.full((n, 1), 0.5, np.float32), _gap_yz(n, rng)])
+    k = 5 + 54 * rng.random(n)
+    d = np.stack([np.ones(n), 1.3 * DEEP_RATIO ** -k, np.zeros(n)], 1)
+    return _rays(o, _unit(d))
+
+
+def _start_x(n, rng):
+    # between triangles j and j + 1, j uniform in 30 .. 59: the triangles past the origin are behind the ray,
+    # so rays differ in the level at which they start to push (j < 31 starts inside the bottom leaf's box)
+    return (2.0 * DEEP_RATIO ** rng.integers(30, DEEP_COUNT, n)).astype(np.float32).reshape(n, 1)
+
+
+def axis_minus(n, seed=23):
+    """Along -x through the gap, from between two triangles of the chain: nothing is hit."""
+    rng = np.random.default_rng(seed)
+    yz = _gap_yz(n, rng)
+    return _rays(np.hstack([_start_x(n, rng), yz]), np.tile(np.array([[-1, 0, 0]], np.float32), (n, 1)))
+
+
+def solid_minus(n, seed=23):
+    """axis_minus shifted by +0.5 in y and z: the closest hit is the first triangle below the origin's x, found
+    after the reference's order has walked to the bottom of the chain and back."""
+    r = axis_minus(n, seed)
+    r[:, 1:3] += np.float32(0.5)
+    return r
+
+
+def tilted_minus(n, seed=24):
+    """tilted_plus's lines walked the other way: from x = 0.5 + 4 * 3^k, outside the common yz box, toward
+    (0.5, y, z) in the gap; the ray enters the box near x = 3^k and meets a triangle soon after."""
+    rng = np.random.default_rng(seed)
+    p = np.hstack([np.full((n, 1), 0.5, np.float32), _gap_yz(n, rng)]).astype(np.float64)
+    k = 5 + 54 * rng.random(n)
+    u = np.stack([np.ones(n), 1.3 * DEEP_RATIO ** -k, np.zeros(n)], 1)
+    o = p + (4.0 * DEEP_RATIO ** k)[:, None] * u
+    return _rays(o.astype(np.float32), _unit(-u))
+
+
+def interleaved(*sets):
+    """Ray i of each set in turn: with three sets every 64-lane wave holds rays of all three."""
+    n = min(s.shape[0] for s in sets)
+    return np.ascontiguousarray(np.stack([s[:n] for s in sets], 1).reshape(-1, 6), np.float32)
 
 
 def write(dirpath):
