@@ -1,10 +1,11 @@
 // rt_query.hip — resident ray queries (rt_query_*) and the one-shot rt_trace_rays on top of
-// them: the ingest, egest and any-hit kernels, the query object and its C ABI.  The closest-hit traversal is
-// the renderer's trace_kernel, compiled in rt_render.hip and launched through rt_common.h; the refit of
-// rt_query_update_triangles is bvh_refit.hip.
+// them: the ingest, egest, hit-record and any-hit kernels, the query object and its C ABI.
+// The closest-hit traversal is the renderer's trace_kernel, compiled in rt_render.hip and launched through
+// rt_common.h; the refit of rt_query_update_triangles is bvh_refit.hip.
 #include "rt_common.h"
 #include "bvh_refit.h"
 #include "bvh_refit_math.h"
+#include "hit_record_math.h"
 
 #include <algorithm>
 #include <cstring>
@@ -58,6 +59,61 @@ __global__ __launch_bounds__(kBlock) void query_egest_kernel(const float2 *__res
         sph = hit && idx < sphere_count;
     }
     const unsigned long long nh = __popcll(__ballot(hit)), ns = __popcll(__ballot(sph));
+    Counters *cs = ctr + ((blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) & (kCtrSlots - 1));
+    if (lane_id() == 0 && nh) {
+        atomicAdd(&cs->hits, nh);
+        if (ns) atomicAdd(&cs->hits_sphere, ns);
+    }
+}
+
+// trace_kernel's {t, index} records -> the caller's hit records (rt_query_closest_hit): one thread
+// per ray evaluates hit_record_math.h on the ray's slots (the o, d the traversal used) and the primitive it
+// hit -- the triangle's three float4s only for index >= S, the sphere's one only for 0 <= index < S -- and
+// stores the fields whose pointer is given (wave-uniform tests).  Counts like query_egest_kernel.  The n x 3
+// rows are stored directly at their 12-B stride: staging a block's rows through LDS for contiguous stores
+// measured no faster (24.8 against 26.0 us per 2 M rays).
+__global__ __launch_bounds__(kBlock) void query_hit_egest_kernel(const float2 *__restrict__ hits, const float4 *__restrict__ geo,
+                                                                 uint32_t n, const float4 *__restrict__ spheres,
+                                                                 const float4 *__restrict__ tris,
+                                                                 const uint16_t *__restrict__ mat_idx, int sphere_count,
+                                                                 rt_hit_out out, Counters *__restrict__ ctr) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    bool is_hit = false, sph = false;
+    if (i < n) {
+        const float2 h = hits[i];
+        const int idx = __float_as_int(h.y);
+        const float4 r0 = geo[(size_t)i * 2], r1 = geo[(size_t)i * 2 + 1];
+        const rt_vec3 o{r0.x, r0.y, r0.z}, d{r0.w, r1.x, r1.y};
+        is_hit = idx >= 0;
+        sph = is_hit && idx < sphere_count;
+        hit::Record rec = hit::miss();
+        if (idx >= sphere_count) {
+            const float4 *tr = tris + (size_t)(idx - sphere_count) * 3;
+            const float4 a = tr[0], b = tr[1], c = tr[2];
+            rec = hit::triangle(o, d, h.x, {a.x, a.y, a.z}, {a.w, b.x, b.y}, {b.z, b.w, c.x}, {c.y, c.z, c.w});
+        } else if (is_hit) {
+            const float4 s = spheres[idx];
+            rec = hit::sphere(o, d, h.x, {s.x, s.y, s.z}, s.w);
+        }
+        if (is_hit) rec.material = (int32_t)mat_idx[idx];
+        if (out.t) out.t[i] = h.x;
+        if (out.index) out.index[i] = idx;
+        if (out.uv) {
+            out.uv[(size_t)i * 2] = rec.u;
+            out.uv[(size_t)i * 2 + 1] = rec.v;
+        }
+        if (out.normal) {
+            float *p = out.normal + (size_t)i * 3;
+            p[0] = rec.normal.x; p[1] = rec.normal.y; p[2] = rec.normal.z;
+        }
+        if (out.position) {
+            float *p = out.position + (size_t)i * 3;
+            p[0] = rec.position.x; p[1] = rec.position.y; p[2] = rec.position.z;
+        }
+        if (out.material) out.material[i] = rec.material;
+        if (out.front_face) out.front_face[i] = rec.front_face;
+    }
+    const unsigned long long nh = __popcll(__ballot(is_hit)), ns = __popcll(__ballot(sph));
     Counters *cs = ctr + ((blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) & (kCtrSlots - 1));
     if (lane_id() == 0 && nh) {
         atomicAdd(&cs->hits, nh);
@@ -325,6 +381,9 @@ struct rt_query {
     DevBuf<float> s_rays, s_tmax, s_t;
     DevBuf<int32_t> s_index;
     DevBuf<uint8_t> s_occ;
+    size_t host_hit_cap = 0;          // closest_hit_host's further staging: uv | normal | position, material
+    DevBuf<float> s_hit;
+    DevBuf<int32_t> s_mat;
     hipEvent_t last = nullptr;
     bool pending = false;             // `last` has been recorded
     int last_kind = 0;                // 0 none (or an update), 1 closest, 2 occluded
@@ -402,6 +461,16 @@ struct rt_query {
                            scene.ds.sphere_count, scene.ctr.p);
         return end(1, n, s);
     }
+    // closest with query_hit_egest_kernel in query_egest_kernel's place: the same counters and stats
+    int closest_hit(const float *d_rays, int n, const rt_hit_out &out, hipStream_t s) {
+        int rc = begin(d_rays, nullptr, n, s);
+        if (rc) return rc;
+        launch_trace_closest(counters, std::min(blocks_for(n), blocks), s, scene.ds, geo.p, live(), queue(), hits.p,
+                             overflow.p, scene.ctr.p);
+        hipLaunchKernelGGL(query_hit_egest_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, s, hits.p, geo.p, (uint32_t)n,
+                           scene.ds.spheres, scene.ds.tris, scene.ds.mat_idx, scene.ds.sphere_count, out, scene.ctr.p);
+        return end(1, n, s);
+    }
     int occluded(const float *d_rays, const float *d_tmax, int n, uint8_t *d_occ, hipStream_t s) {
         int rc = begin(d_rays, d_tmax, n, s);
         if (rc) return rc;
@@ -435,6 +504,41 @@ struct rt_query {
         if ((rc = closest(s_rays.p, n, s_t.p, s_index.p, s))) return rc;
         if (t) HIPCHK(hipMemcpyAsync(t, s_t.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s));
         if (index) HIPCHK(hipMemcpyAsync(index, s_index.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return RT_OK;
+    }
+    int reserve_host_hit(int n) {
+        int rc = reserve_host(n);
+        if (rc || (size_t)n <= host_hit_cap) return rc;
+        HIPCHK(hipSetDevice(scene.device));
+        const size_t want = std::max<size_t>({(size_t)n, 2 * host_hit_cap, (size_t)kBlock});
+        host_hit_cap = 0;
+        if ((rc = s_hit.alloc(want * 8)) || (rc = s_mat.alloc(want))) return rc;
+        host_hit_cap = want;
+        return RT_OK;
+    }
+    int closest_hit_host(const float *rays, int n, const rt_hit_out &out) {
+        int rc = reserve_host_hit(n);
+        if (rc) return rc;
+        hipStream_t s = stream;
+        rt_hit_out d{};
+        if (out.t) d.t = s_t.p;
+        if (out.index) d.index = s_index.p;
+        if (out.uv) d.uv = s_hit.p;
+        if (out.normal) d.normal = s_hit.p + 2 * host_hit_cap;
+        if (out.position) d.position = s_hit.p + 5 * host_hit_cap;
+        if (out.material) d.material = s_mat.p;
+        if (out.front_face) d.front_face = s_occ.p;
+        HIPCHK(hipMemcpyAsync(s_rays.p, rays, (size_t)n * 6 * sizeof(float), hipMemcpyHostToDevice, s));
+        if ((rc = closest_hit(s_rays.p, n, d, s))) return rc;
+        const size_t m = (size_t)n;
+        if (out.t) HIPCHK(hipMemcpyAsync(out.t, d.t, m * sizeof(float), hipMemcpyDeviceToHost, s));
+        if (out.index) HIPCHK(hipMemcpyAsync(out.index, d.index, m * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        if (out.uv) HIPCHK(hipMemcpyAsync(out.uv, d.uv, m * 2 * sizeof(float), hipMemcpyDeviceToHost, s));
+        if (out.normal) HIPCHK(hipMemcpyAsync(out.normal, d.normal, m * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
+        if (out.position) HIPCHK(hipMemcpyAsync(out.position, d.position, m * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
+        if (out.material) HIPCHK(hipMemcpyAsync(out.material, d.material, m * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        if (out.front_face) HIPCHK(hipMemcpyAsync(out.front_face, d.front_face, m, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         return RT_OK;
     }
@@ -572,6 +676,22 @@ int rt_query_occluded_host(rt_query *q, const float *rays, const float *tmax, in
     if (n == 0) return RT_OK;
     if (!rays || !occluded) return rtamd::fail(RT_E_INVALID, "rt_query_occluded_host: null pointer");
     return q->occluded_host(rays, tmax, n, occluded);
+}
+
+int rt_query_closest_hit(rt_query *q, const float *d_rays, int32_t n, const rt_hit_out *d_out, void *hip_stream) {
+    if (!q) return rtamd::fail(RT_E_INVALID, "rt_query_closest_hit: null query object");
+    if (n < 0) return rtamd::fail(RT_E_INVALID, "rt_query_closest_hit: negative ray count");
+    if (n == 0) return RT_OK;
+    if (!d_rays || !d_out) return rtamd::fail(RT_E_INVALID, "rt_query_closest_hit: null pointer");
+    return q->closest_hit(d_rays, n, *d_out, static_cast<hipStream_t>(hip_stream));
+}
+
+int rt_query_closest_hit_host(rt_query *q, const float *rays, int32_t n, const rt_hit_out *out) {
+    if (!q) return rtamd::fail(RT_E_INVALID, "rt_query_closest_hit_host: null query object");
+    if (n < 0) return rtamd::fail(RT_E_INVALID, "rt_query_closest_hit_host: negative ray count");
+    if (n == 0) return RT_OK;
+    if (!rays || !out) return rtamd::fail(RT_E_INVALID, "rt_query_closest_hit_host: null pointer");
+    return q->closest_hit_host(rays, n, *out);
 }
 
 int rt_query_stats(rt_query *q, rt_stats *stats) {

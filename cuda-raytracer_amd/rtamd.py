@@ -82,6 +82,26 @@ class RtStats(C.Structure):
                 for n, t in self._fields_ if n != "reserved"}
 
 
+class RtHitOut(C.Structure):
+    """rt_hit_out: one optional output pointer per hit-record field."""
+    _fields_ = [(n, P) for n in ("t", "index", "uv", "normal", "position", "material", "front_face")]
+
+
+HIT_FIELDS = tuple(n for n, _ in RtHitOut._fields_)
+# field -> (shape after n, numpy dtype as the library writes it); front_face is returned as bool
+HIT_SHAPES = {"t": ((), np.float32), "index": ((), np.int32), "uv": ((2,), np.float32), "normal": ((3,), np.float32),
+              "position": ((3,), np.float32), "material": ((), np.int32), "front_face": ((), np.uint8)}
+
+
+def _hit_fields(fields):
+    """The requested hit-record fields as a tuple in HIT_FIELDS order; an unknown name raises ValueError."""
+    names = (fields,) if isinstance(fields, str) else tuple(fields)
+    for k in names:
+        if k not in HIT_SHAPES:
+            raise ValueError("unknown hit-record field %r (known: %s)" % (k, ", ".join(HIT_FIELDS)))
+    return tuple(k for k in HIT_FIELDS if k in names)
+
+
 _lib = None
 
 
@@ -236,6 +256,31 @@ class Scene:
         f = lib().rt_scene_refit
         f.argtypes = [P, P, I32]
         _check(f(self.h, _ptr(a), a.shape[0]))
+
+    def hit_records(self, rays, t, index, fields=HIT_FIELDS):
+        """rt_scene_hit_records: the hit records of given closest hits on this host scene, no GPU:
+        rays (n, 6) float32, t (n,) float32 and index (n,) int32 as closest / trace_rays return them, all numpy
+        and contiguous.  Returns a dict of the requested fields ("t" and "index" are the arguments' copies)."""
+        names = _hit_fields(fields)
+        a = RayQuery._rays_np(rays)
+        n = a.shape[0]
+        tt, ii = np.asarray(t), np.asarray(index)
+        if tt.dtype != np.float32 or tt.shape != (n,) or not tt.flags["C_CONTIGUOUS"]:
+            raise ValueError("t must be a contiguous float32 array of shape (n,)")
+        if ii.dtype != np.int32 or ii.shape != (n,) or not ii.flags["C_CONTIGUOUS"]:
+            raise ValueError("index must be a contiguous int32 array of shape (n,)")
+        out = {k: np.zeros((n,) + HIT_SHAPES[k][0], HIT_SHAPES[k][1]) for k in names if k not in ("t", "index")}
+        ho = RtHitOut(**{k: _ptr(v) for k, v in out.items()})
+        f = lib().rt_scene_hit_records
+        f.argtypes = [P, P, P, P, I32, P]
+        _check(f(self.ptr, _ptr(a), _ptr(tt), _ptr(ii), n, C.byref(ho)))
+        if "t" in names:
+            out["t"] = tt.copy()
+        if "index" in names:
+            out["index"] = ii.copy()
+        if "front_face" in out:
+            out["front_face"] = out["front_face"].view(np.bool_)
+        return {k: out[k] for k in names}
 
     def arrays(self):
         v = self.view
@@ -403,7 +448,9 @@ class RayQuery:
     torch.Tensor on cuda:<device> (float32, shape (n, 6), contiguous; anything else raises ValueError,
     nothing is copied or converted silently).  For a tensor the results are torch tensors on that device
     (float32 t, int32 index, bool mask) and the work is enqueued on torch.cuda.current_stream(device)
-    without any synchronisation: they are ready in stream order, like any torch op's."""
+    without any synchronisation: they are ready in stream order, like any torch op's.
+    closest_hit(rays, fields=...) is closest with the hit record (uv, normal, position, material, front_face),
+    under the same rules; update(vertices) moves the triangles under the frozen BVH topology."""
 
     def __init__(self, scene, device=0, counters=False, L=None):
         self.L = L or lib()
@@ -472,6 +519,35 @@ class RayQuery:
         idx = np.zeros(n, np.int32)
         _check(self.L.rt_query_closest_host(self.h, _ptr(a), n, _ptr(t), _ptr(idx)), self.L)
         return t, idx
+
+    def closest_hit(self, rays, fields=HIT_FIELDS):
+        """rt_query_closest_hit: the closest hit with its hit record.  Returns a dict of the
+        requested fields: t (n,) float32, index (n,) int32, uv (n, 2), normal (n, 3) (unflipped), position (n, 3)
+        float32, material (n,) int32, front_face (n,) bool; a miss has index -1, material -1 and zeros.  Fields
+        that are not requested are neither computed into memory nor allocated; fields=() only traverses and
+        counts.  Tensors in, tensors out on torch.cuda.current_stream(device) without any synchronisation; a
+        numpy array takes the _host path (blocking) and gives numpy.  An unknown field name raises ValueError."""
+        names = _hit_fields(fields)
+        f = self.L
+        if _is_tensor(rays):
+            import torch
+            n = self.check_tensor(rays, self.device)
+            dt = {np.float32: torch.float32, np.int32: torch.int32, np.uint8: torch.bool}
+            out = {k: torch.empty((n,) + HIT_SHAPES[k][0], dtype=dt[HIT_SHAPES[k][1]], device=rays.device) for k in names}
+            ho = RtHitOut(**{k: v.data_ptr() for k, v in out.items()})
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            f.rt_query_closest_hit.argtypes = [P, P, I32, P, P]
+            _check(f.rt_query_closest_hit(self.h, P(rays.data_ptr()), n, C.byref(ho), P(stream) if stream else None), f)
+            return out
+        a = self._rays_np(rays)
+        n = a.shape[0]
+        out = {k: np.zeros((n,) + HIT_SHAPES[k][0], HIT_SHAPES[k][1]) for k in names}
+        ho = RtHitOut(**{k: _ptr(v) for k, v in out.items()})
+        f.rt_query_closest_hit_host.argtypes = [P, P, I32, P]
+        _check(f.rt_query_closest_hit_host(self.h, _ptr(a), n, C.byref(ho)), f)
+        if "front_face" in out:
+            out["front_face"] = out["front_face"].view(np.bool_)
+        return out
 
     def occluded(self, rays, tmax=None):
         """Any hit before tmax (per ray; None = 1e30, i.e. anything at all): a bool mask."""

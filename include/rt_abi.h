@@ -360,6 +360,55 @@ int rt_query_update_triangles(rt_query *q, const float *d_vertices, int32_t tria
 int rt_query_update_triangles_host(rt_query *q, const float *vertices, int32_t triangle_count);
 int rt_query_read_geometry(rt_query *q, rt_triangle *triangles_out, rt_bvh_node *bvh_out);
 
+/* Hit records: the closest hit with what a caller needs of the surface.  The presence of these
+ * symbols is the feature probe; RT_ABI_VERSION and every existing struct are unchanged.  No reference
+ * counterpart as an interface; every field restates what the reference forms at the hit (scene.cu:160-195,
+ * :398-418).
+ * For ray i with origin o and direction d let (t, index) be exactly what rt_query_closest returns and S the
+ * scene's sphere count.  All arithmetic is float32, each operation rounded once, no contraction;
+ * dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z; cross(a, b) = (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z,
+ * a.x*b.y - a.y*b.x).
+ *   t, index     unchanged (1e30 and -1 on a miss).
+ *   miss         (index < 0): uv = (+0, +0), normal = position = (+0, +0, +0), material = -1, front_face = 0.
+ *   position     o + t * d per component, a multiply then an add (scene.cu:398).
+ *   triangle     record k = index - S (p1, e1 = p2p1, e2 = p3p1, normal):
+ *                  h = cross(d, e2); a = dot(h, e1); f = 1 / a; s = o - p1;
+ *                  u = dot(s, h) * f; q = cross(s, e1); v = dot(d, q) * f          (scene.cu:166-183)
+ *                uv = (u, v): the hit lies at p1 + u e1 + v e2.  normal = the record's, unflipped
+ *                (scene.cu:409-410).
+ *   sphere       uv = (+0, +0); normal = (1 / radius) * (position - center) (scene.cu:405).
+ *   front_face   dot(normal, d) < 0 (scene.cu:418).  The normal is returned unflipped: the reference's shading
+ *                normal is its negation where front_face == 0.
+ *   material     material_indices[index] as int32 (scene.cu:413).
+ * The geometry is the object's current resident geometry: after rt_query_update_triangles the records come
+ * from the refitted triangles (a zero-area triangle has a NaN normal and a = 0).  A NaN is any NaN: the sign
+ * and payload of a NaN an operation produced are the processor's.
+ * rt_hit_out: one output array per field, every pointer optional (NULL = not written); an rt_hit_out whose
+ * fields are all NULL is allowed, the call then only traverses and counts.
+ * rt_query_closest_hit follows every rule of rt_query_closest (device pointers on q's device, enqueued on
+ * hip_stream, joins the event chain, allocates nothing once the scratch holds n rays, never waits on the
+ * host; n == 0 is RT_OK and touches no pointer; a null object, n < 0, or a null d_rays or d_out with n > 0
+ * is RT_E_INVALID before any HIP call).  d_out is a host pointer to a struct of device pointers, read
+ * before the call returns.  rt_query_stats after it returns what it returns after rt_query_closest on the
+ * same rays.  The _host variant takes host pointers throughout, stages through buffers of the object and
+ * blocks.
+ * rt_scene_hit_records is the host twin: the records of given (t, index) on a host scene, no GPU, bit for
+ * bit what the device call writes for the same (t, index); out->t and out->index are ignored.  An index that
+ * is not below sphere_count + triangle_count is RT_E_INVALID and nothing is written. */
+typedef struct {            /* every pointer optional: NULL = not written */
+    float   *t;             /* n        */
+    int32_t *index;         /* n        */
+    float   *uv;            /* n x 2    */
+    float   *normal;        /* n x 3    */
+    float   *position;      /* n x 3    */
+    int32_t *material;      /* n        */
+    uint8_t *front_face;    /* n, 0 / 1 */
+} rt_hit_out;
+int rt_query_closest_hit(rt_query *q, const float *d_rays, int32_t n, const rt_hit_out *d_out, void *hip_stream);
+int rt_query_closest_hit_host(rt_query *q, const float *rays, int32_t n, const rt_hit_out *out);
+int rt_scene_hit_records(const rt_scene *scene, const float *rays, const float *t, const int32_t *index,
+                         int32_t n, const rt_hit_out *out);
+
 /* Replaces the bloom block of main (raytracing.cu:356-393, kernels :21-74): high-pass
  * (luminance > threshold), clamped box blur of `radius` horizontally then vertically,
  * add back.  fb is a host W*H*3 buffer, updated in place. */

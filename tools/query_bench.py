@@ -13,6 +13,15 @@ warm-up, `--calls` times each in alternation (one call of every leg per round, t
   occluded_any      the same rays, tmax = None
   closest_hemi      RayQuery.closest on the hemisphere rays (the closest-hit cost of the same rays)
 
+and, on both ray sets (the hemisphere legs carry the suffix _hemi), the hit records of DESIGN §13:
+
+  closest_hit_all         RayQuery.closest_hit with every field
+  closest_hit_tiuv        the same with t, index and uv only
+  closest_torch_records   a caller's alternative: RayQuery.closest, then the same fields in torch ops over
+                          Scene.arrays() tensors (torch_records)
+
+with the added time of each over the closest leg of the same rays and rounds (hit_added_ms).
+
 Device calls are timed with HIP events on the calling stream (ms, median and min) and on the host's wall
 clock around call + synchronise; the host call on the wall clock only.  Prints one JSON line and writes it to
 profiles/query/query_bench.json (or --out).
@@ -76,6 +85,34 @@ def hemisphere_rays(rays, t, index, tris, sphere_count, gen):
     return torch.cat([p, w], dim=1).contiguous()
 
 
+def torch_records(q, rays, tris, spheres, mat_idx):
+    """A caller's alternative to RayQuery.closest_hit: closest, then the hit-record fields in torch ops
+    over Scene.arrays() tensors -- the gathers and the arithmetic, not the library's rounding."""
+    t, index = q.closest(rays)
+    S = spheres.shape[0]
+    hit, is_tri = index >= 0, index >= S
+    o, d = rays[:, :3], rays[:, 3:]
+    pos = o + t.unsqueeze(1) * d
+    if tris.shape[0]:
+        rec = tris[(index - S).clamp_min(0).long()]
+        p1, e1, e2, normal = rec[:, 0:3], rec[:, 3:6], rec[:, 6:9], rec[:, 9:12]
+        h = torch.linalg.cross(d, e2)
+        f = 1 / (h * e1).sum(1)
+        s = o - p1
+        uv = torch.stack([(s * h).sum(1) * f, (d * torch.linalg.cross(s, e1)).sum(1) * f], 1)
+        uv = torch.where(is_tri.unsqueeze(1), uv, torch.zeros_like(uv))
+    else:
+        uv, normal = torch.zeros((rays.shape[0], 2), device=rays.device), torch.zeros_like(pos)
+    if S:
+        sp = spheres[index.clamp(0, S - 1).long()]
+        normal = torch.where(is_tri.unsqueeze(1), normal, (pos - sp[:, :3]) / sp[:, 3:4])
+    zero = torch.zeros_like(pos)
+    normal = torch.where(hit.unsqueeze(1), normal, zero)
+    return {"t": t, "index": index, "uv": uv, "normal": normal, "position": torch.where(hit.unsqueeze(1), pos, zero),
+            "material": torch.where(hit, mat_idx[index.clamp_min(0).long()], torch.full_like(index, -1)),
+            "front_face": hit & ((normal * d).sum(1) < 0)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=20)
@@ -132,6 +169,16 @@ def main():
             ("occluded_tmax", nh, device_call(lambda: q.occluded(hemi, tmax))),
             ("occluded_any", nh, device_call(lambda: q.occluded(hemi))),
             ("closest_hemi", nh, device_call(lambda: q.closest(hemi)))]
+    # hit records, when the library has them (the symbol is the feature probe: an A/B run on an
+    # older library times the legs above alone)
+    has_hit = hasattr(rtamd.lib(), "rt_query_closest_hit")
+    if has_hit:
+        tris_t, sph_t = torch.from_numpy(arr["triangles"]).to(dev), torch.from_numpy(arr["spheres"]).to(dev)
+        mat_t = torch.from_numpy(arr["material_indices"].astype(np.int32)).to(dev)
+        for tag, r, count in (("", rays, n), ("_hemi", hemi, nh)):
+            legs += [("closest_hit_all" + tag, count, device_call(lambda r=r: q.closest_hit(r))),
+                     ("closest_hit_tiuv" + tag, count, device_call(lambda r=r: q.closest_hit(r, fields=("t", "index", "uv")))),
+                     ("closest_torch_records" + tag, count, device_call(lambda r=r: torch_records(q, r, tris_t, sph_t, mat_t)))]
     times = {name: ([], []) for name, _, _ in legs}
     shuffler = random.Random(args.seed)
     last = {}
@@ -167,6 +214,20 @@ def main():
     result["occluded_any_equals_closest_hit"] = bool(torch.equal(last["occluded_any"], last["closest_hemi"][1] >= 0))
     result["speedup_closest_device_over_trace_rays_host_wall"] = (
         result["legs"]["trace_rays_host"]["wall_ms_median"] / result["legs"]["closest_device"]["wall_ms_median"])
+    if has_hit:
+        # the added time of closest_hit over closest in the same rounds, and against the torch alternative's
+        for tag, base in (("", "closest_device"), ("_hemi", "closest_hemi")):
+            ms = {k: result["legs"][k + tag]["event_ms_median"] for k in ("closest_hit_all", "closest_hit_tiuv", "closest_torch_records")}
+            b = result["legs"][base]["event_ms_median"]
+            result["hit_added_ms" + tag] = {k: v - b for k, v in ms.items()}
+            result["hit_added_ratio_torch_over_closest_hit_all" + tag] = (
+                (ms["closest_torch_records"] - b) / (ms["closest_hit_all"] - b) if ms["closest_hit_all"] > b else None)
+            result["hit_ratio_torch_over_closest_hit_all" + tag] = ms["closest_torch_records"] / ms["closest_hit_all"]
+            got, alt = last["closest_hit_all" + tag], last["closest_torch_records" + tag]
+            fin = torch.isfinite(got["uv"]).all(1) & torch.isfinite(alt["uv"]).all(1)
+            result["torch_records_max_abs_diff" + tag] = {
+                k: float((got[k][fin] - alt[k][fin]).abs().max()) for k in ("uv", "normal", "position")}
+            result["torch_records_material_equal" + tag] = bool(torch.equal(got["material"], alt["material"]))
     q.close()
     line = json.dumps(result)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
