@@ -1,0 +1,100 @@
+// cpu_query.hip — rt_scene_multi_hit, the host twin of rt_query_multi_hit, host-only.
+//
+// The reference traversal (scene.cu:338-372, :134-241) with `closest` held at the ray's bound B and never
+// updated, run to the end: every accepted primitive is a hit.  The per-ray arithmetic is the shared
+// __host__ __device__ code in rt_device.h (ray_sphere, ray_triangle, slab), so the accepted set and every t
+// are the device kernel's bit for bit; the node array is the scene's own (rt_scene.bvh), walked with a plain
+// stack -- the set does not depend on the order.  The hits are then sorted by the key (t', index) of rt_abi.h.
+#include "rt_abi.h"
+#include "rt_device.h"
+
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#pragma clang fp contract(off)
+
+namespace rtamd {
+int fail(int code, const std::string &msg);
+}
+
+using namespace rtd;
+
+namespace {
+
+struct Hit { uint32_t key; int32_t index; float t; };
+
+V3 vec(const rt_vec3 &v) { return v3(v.x, v.y, v.z); }
+
+// t' of rt_abi.h: t's bits, every NaN as one pattern
+uint32_t key_of(float t) {
+    uint32_t b;
+    std::memcpy(&b, &t, 4);
+    return t != t ? 0x7FC00000u : b;
+}
+
+void all_hits(const rt_scene &s, V3 o, V3 d, float B, std::vector<Hit> &hits, std::vector<int32_t> &stack) {
+    hits.clear();
+    for (int i = 0; i < s.sphere_count; i++) {
+        float t;
+        if (ray_sphere(o, d, vec(s.spheres[i].center), s.spheres[i].radius, B, t)) hits.push_back({key_of(t), i, t});
+    }
+    if (0.0f >= B || s.bvh_node_count <= 0) return;
+    const float ix = 1 / d.x, iy = 1 / d.y, iz = 1 / d.z;
+    stack.clear();
+    stack.push_back(0);
+    while (!stack.empty()) {
+        const rt_bvh_node &nd = s.bvh[stack.back()];
+        stack.pop_back();
+        if (nd.child2 <= nd.child1) {
+            for (int i = nd.child2; i < nd.child1; i++) {
+                const rt_triangle &tr = s.triangles[i];
+                float t;
+                if (ray_triangle(o, d, vec(tr.p1), vec(tr.p2p1), vec(tr.p3p1), B, t))
+                    hits.push_back({key_of(t), s.sphere_count + i, t});
+            }
+            continue;
+        }
+        for (const int32_t c : {nd.child1, nd.child2}) {
+            const rt_bvh_node &b = s.bvh[c];
+            float entry;
+            if (slab(b.min_bound.x, b.min_bound.y, b.min_bound.z, b.max_bound.x, b.max_bound.y, b.max_bound.z, o, ix, iy,
+                     iz, B, entry) &&
+                !(entry >= B))
+                stack.push_back(c);
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int rt_scene_multi_hit(const rt_scene *s, const float *rays, const float *tmax, int32_t n, int32_t k,
+                                  const rt_multi_hit_out *out) {
+    if (!s) return rtamd::fail(RT_E_INVALID, "rt_scene_multi_hit: null scene");
+    if (n < 0) return rtamd::fail(RT_E_INVALID, "rt_scene_multi_hit: negative ray count");
+    if (k < 1 || k > RT_MULTI_HIT_MAX)
+        return rtamd::fail(RT_E_INVALID, "rt_scene_multi_hit: k " + std::to_string(k) + " is outside 1.." +
+                                             std::to_string(RT_MULTI_HIT_MAX));
+    if (n == 0) return RT_OK;
+    if (!rays || !out) return rtamd::fail(RT_E_INVALID, "rt_scene_multi_hit: null pointer");
+    if ((int64_t)n * k > INT32_MAX)
+        return rtamd::fail(RT_E_INVALID, "rt_scene_multi_hit: n * k = " + std::to_string((int64_t)n * k) + " does not fit int32");
+    std::vector<Hit> hits;
+    std::vector<int32_t> stack;
+    for (int32_t i = 0; i < n; i++) {
+        const float *r = rays + (size_t)i * 6;
+        float B = 1e30f;
+        if (tmax) B = tmax[i] <= 1e30f ? tmax[i] : 1e30f;
+        all_hits(*s, v3(r[0], r[1], r[2]), v3(r[3], r[4], r[5]), B, hits, stack);
+        std::sort(hits.begin(), hits.end(),
+                  [](const Hit &a, const Hit &b) { return a.key != b.key ? a.key < b.key : a.index < b.index; });
+        if (out->count) out->count[i] = (int32_t)hits.size();
+        for (int32_t j = 0; j < k; j++) {
+            const bool have = (size_t)j < hits.size();
+            if (out->t) out->t[(size_t)i * k + j] = have ? hits[j].t : 1e30f;
+            if (out->index) out->index[(size_t)i * k + j] = have ? hits[j].index : -1;
+        }
+    }
+    return RT_OK;
+}

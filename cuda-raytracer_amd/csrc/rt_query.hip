@@ -1,5 +1,6 @@
 // rt_query.hip — resident ray queries (rt_query_*) and the one-shot rt_trace_rays on top of
-// them: the ingest, egest, hit-record and any-hit kernels, the query object and its C ABI.
+// them: the ingest, egest, hit-record, any-hit and multi-hit kernels, the query object
+// and its C ABI.
 // The closest-hit traversal is the renderer's trace_kernel, compiled in rt_render.hip and launched through
 // rt_common.h; the refit of rt_query_update_triangles is bvh_refit.hip.
 #include "rt_common.h"
@@ -359,6 +360,269 @@ __global__ __launch_bounds__(kBlock) RT_TRACE_ATTR void anyhit_kernel(DevScene S
     if (lane_id() == 0 && no) atomicAdd(&cs->hits, no);
 }
 
+// Every hit before the ray's bound B (rt_query_multi_hit): anyhit_kernel's traversal -- the same
+// predicates with `closest` held at B, the same queue, refill, root step, record load, slab fold, near-first
+// order and 4-B stack -- without its exits: the sphere loop runs to the end and a lane retires only when its
+// stack is empty, so it enumerates the whole accepted set, which is fixed whatever the order.
+// An accepted (t, index) is inserted into the ray's list of its K smallest hits by the key (t', index), t' =
+// t's bits with every NaN as 0x7FC00000 (accepted t is NaN or >= 0.005: unsigned order is numeric order, NaNs
+// last).  The list lives in rows slot*K.. of lt[] and li[] -- the caller's t and index arrays, or the object's
+// scratch for the one the caller left out -- and the lane reads and writes only its own earlier stores.  It
+// keeps its count and the key of its K-th record in registers: once the list is full a hit that is not below
+// that key costs one compare.  With lt == nullptr (wave-uniform) nothing is kept and the lane only counts.
+// At retire the lane pads entries [min(count, K), K) with (1e30, -1) and stores the count; like anyhit_kernel's
+// answers these stores wait for the lane's next refill.
+// Counters (COUNT): Pn, Iv, Tt and S sphere tests per ray of the full traversal, order-independent.
+// The loop, node_step and pop_loop are anyhit_kernel's text, repeated here and not shared through a template:
+// anyhit_kernel has to compile to the registers and occupancy it was tuned at (profiles/multihit/kernel_resources.txt).
+__device__ __forceinline__ uint32_t multihit_key(float t) { return t != t ? 0x7FC00000u : __float_as_uint(t); }
+
+template <bool COUNT>
+__global__ __launch_bounds__(kBlock) RT_TRACE_ATTR void multihit_kernel(DevScene S, const float4 *__restrict__ geo,
+                                                                        const uint32_t *__restrict__ live_count,
+                                                                        uint32_t *__restrict__ queue, int K, float *lt,
+                                                                        int32_t *li, int32_t *__restrict__ count_out,
+                                                                        uint32_t *__restrict__ overflow,
+                                                                        Counters *__restrict__ ctr) {
+    __shared__ uint32_t stack[(kAnyStackLds + 1) * kBlock];   // + one scratch entry per lane
+    uint32_t *col = stack + threadIdx.x;
+    // entry e >= kAnyStackLds of this lane: overflow[(e - kAnyStackLds) * lanes + lane]
+    const uint32_t lanes = gridDim.x * kBlock, gl = blockIdx.x * kBlock + threadIdx.x;
+    const uint32_t L = __builtin_amdgcn_readfirstlane(*live_count);
+    const uint32_t waves = gridDim.x * (kBlock / 64);
+    const uint32_t chunk = min((uint32_t)kChunkMax, max((uint32_t)kChunkMin, (L / (4 * waves) + 63) & ~63u));
+    uint32_t shard = blockIdx.x % kQueues, tried = 0;
+    uint32_t q_next = 0, q_end = 0;     // this wave's current chunk (wave-uniform)
+    bool exhausted = false;
+    int slot = -1;                      // < 0: lane has no ray; <= -2: done with slot -2 - slot, row not yet finished
+    V3 o{0, 0, 0}, d{0, 0, 0};
+    float ix = 0, iy = 0, iz = 0, B = 0;
+    bool finite_inv = true;
+    bool wave_nonfinite = false;
+    int sp = 0;
+    uint32_t ref = 0;
+    int ti = 0, te = 0;                 // the lane is in a leaf while ti < te
+    int cnt = 0;                        // accepted primitives of the lane's ray so far
+    uint32_t kth_key = 0;               // key of list entry K - 1, valid once cnt >= K
+    int kth_idx = 0;
+    unsigned pn = 0, iv = 0, tt = 0, stn = 0, nhit = 0;
+    const bool keep = lt != nullptr;
+    // One accepted primitive of the lane's ray `slot` (>= 0).
+    auto insert = [&](float t, int idx) {
+        if (keep) {
+            const uint32_t key = multihit_key(t);
+            int j = -1;                 // the entry the new record would take before any shift
+            if (cnt < K) j = cnt;
+            else if (key < kth_key || (key == kth_key && idx < kth_idx)) j = K - 1;
+            if (j >= 0) {
+                float *rt = lt + (size_t)slot * K;
+                int32_t *ri = li + (size_t)slot * K;
+                while (j > 0) {
+                    const float pt = rt[j - 1];
+                    const int pi = ri[j - 1];
+                    const uint32_t pk = multihit_key(pt);
+                    if (!(pk > key || (pk == key && pi > idx))) break;
+                    if (j == K - 1) { kth_key = pk; kth_idx = pi; }
+                    rt[j] = pt;
+                    ri[j] = pi;
+                    j--;
+                }
+                if (j == K - 1) { kth_key = key; kth_idx = idx; }
+                rt[j] = t;
+                ri[j] = idx;
+            }
+        }
+        cnt++;
+    };
+    // The row of a finished ray: padding and count.
+    auto finish = [&](int s) {
+        if (keep) {
+            for (int j = min(cnt, K); j < K; j++) {
+                lt[(size_t)s * K + j] = 1e30f;
+                li[(size_t)s * K + j] = -1;
+            }
+        }
+        if (count_out) count_out[s] = cnt;
+        nhit += cnt > 0 ? 1u : 0u;
+    };
+    auto node_step = [&](float4 a, float4 b, float4 c, uint2 kids) -> bool {
+        if (COUNT) iv++;
+        float t0, t1;
+        bool h0, h1;
+        slab_pair(a, b, c, o, ix, iy, iz, B, h0, h1, t0, t1);
+        if (__builtin_expect(wave_nonfinite, 0)) {
+            float u0, u1;
+            const bool g0 = slab(a.x, a.z, b.x, b.z, c.x, c.z, o, ix, iy, iz, B, u0);
+            const bool g1 = slab(a.y, a.w, b.y, b.w, c.y, c.w, o, ix, iy, iz, B, u1);
+            if (!finite_inv) { h0 = g0; h1 = g1; t0 = u0; t1 = u1; }
+        }
+        const bool e0 = h0 && !(t0 >= B), e1 = h1 && !(t1 >= B);
+        const bool both = e0 && e1, any = e0 || e1;
+        const bool sel1 = e1 && (!e0 || t1 < t0);
+        const uint32_t next_ref = sel1 ? kids.y : kids.x, far_ref = sel1 ? kids.x : kids.y;
+        // written either way (above the top when not pushed; entry kAnyStackLds is a scratch slot)
+        col[min(sp, kAnyStackLds) * kBlock] = far_ref;
+        if (__builtin_expect(both && sp >= kAnyStackLds, 0)) overflow[(sp - kAnyStackLds) * lanes + gl] = far_ref;
+        if (both) sp++;
+        bool need = !any;
+        if (any) {
+            ref = next_ref;
+            if (COUNT) pn++;
+            if (ref & kLeaf) {
+                leaf_range(S, ref, ti, te);
+                need = ti == te;
+            }
+        }
+        return need;
+    };
+    // Pop: every entry on the stack is entered; an empty stack ends the ray.
+    auto pop_loop = [&](bool need) {
+        while (need) {
+            const bool empty = sp == 0;
+            sp = empty ? 0 : sp - 1;
+            uint32_t e = col[min(sp, kAnyStackLds) * kBlock];
+            asm volatile("" : "+v"(e));   // keeps the LDS read an LDS read (see trace_kernel)
+            if (__builtin_expect(__ballot(sp >= kAnyStackLds) != 0, 0)) {   // wave-uniform, rare
+                if (sp >= kAnyStackLds) e = overflow[(sp - kAnyStackLds) * lanes + gl];
+            }
+            slot = empty ? -2 - slot : slot;
+            ref = empty ? ref : e;
+            if (COUNT) pn += empty ? 0u : 1u;
+            const bool leaf = !empty && (ref & kLeaf);
+            if (__builtin_expect(leaf && (ref & kBigLeaf), 0)) {
+                leaf_range(S, ref, ti, te);
+            } else {
+                ti = leaf ? (int)(ref & 0xFFFFFFu) : ti;
+                te = leaf ? ti + (int)((ref >> 24) & 0x3Fu) : te;
+            }
+            need = leaf && ti == te;
+        }
+    };
+    const bool root_internal = !(S.root_ref & kLeaf);
+    float4 ra{0, 0, 0, 0}, rb{0, 0, 0, 0}, rc{0, 0, 0, 0};
+    uint2 rk{0, 0};
+    if (root_internal) {
+        const float4 *rr = S.nodes + (size_t)S.root_ref * 4;
+        const float4 x0 = rr[0], x1 = rr[1], x2 = rr[2];
+        const uint2 k = *reinterpret_cast<const uint2 *>(rr + 3);
+#define RT_U(v) __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)))
+        ra = make_float4(RT_U(x0.x), RT_U(x0.y), RT_U(x0.z), RT_U(x0.w));
+        rb = make_float4(RT_U(x1.x), RT_U(x1.y), RT_U(x1.z), RT_U(x1.w));
+        rc = make_float4(RT_U(x2.x), RT_U(x2.y), RT_U(x2.z), RT_U(x2.w));
+#undef RT_U
+        rk = make_uint2(__builtin_amdgcn_readfirstlane(k.x), __builtin_amdgcn_readfirstlane(k.y));
+    }
+    while (true) {
+        // ---- refill idle lanes (wave-uniform control flow)
+        unsigned long long idle = __ballot(slot < 0);
+        if (!exhausted && __popcll(idle) >= kRefill) {
+            if (slot <= -2) {             // rows of the lanes that finished since the last refill
+                finish(-2 - slot);
+                slot = -1;
+            }
+            bool fresh = false;
+            while (idle && !exhausted) {
+                if (q_next >= q_end) {
+                    const uint32_t seg_lo = (uint32_t)(((uint64_t)L * shard) / kQueues);
+                    const uint32_t seg_hi = (uint32_t)(((uint64_t)L * (shard + 1)) / kQueues);
+                    uint32_t c = 0;
+                    if (lane_id() == 0) c = atomicAdd(queue + shard * kQueueStride, chunk);
+                    c = __builtin_amdgcn_readfirstlane(__shfl(c, 0)) + seg_lo;
+                    if (c >= seg_hi) {
+                        shard = (shard + 1) % kQueues;
+                        if (++tried == kQueues) exhausted = true;
+                        continue;
+                    }
+                    q_next = c;
+                    q_end = min(c + chunk, seg_hi);
+                }
+                const uint32_t avail = q_end - q_next;
+                const uint32_t r = rank_below(idle);
+                const bool take = slot < 0 && r < avail;
+                const unsigned long long took = __ballot(take);
+                if (take) { slot = (int)(q_next + r); fresh = true; }
+                q_next += (uint32_t)__popcll(took);
+                idle &= ~took;
+            }
+            if (fresh) {
+                const float4 *rp = geo + (size_t)slot * 2;
+                const float4 r0 = rp[0], r1 = rp[1];
+                o = v3(r0.x, r0.y, r0.z);
+                d = v3(r0.w, r1.x, r1.y);
+                B = r1.z;
+                ix = 1 / d.x; iy = 1 / d.y; iz = 1 / d.z;
+                finite_inv = __builtin_isfinite(ix) && __builtin_isfinite(iy) && __builtin_isfinite(iz);
+                cnt = 0;
+                for (int i = 0; i < S.sphere_count; i++) {
+                    const float4 sph = S.spheres[i];
+                    float t;
+                    if (COUNT) stn++;
+                    if (ray_sphere(o, d, v3(sph.x, sph.y, sph.z), sph.w, B, t)) insert(t, i);
+                }
+                ref = S.root_ref;
+                sp = 0;
+                ti = te = 0;
+                // the root is popped with distance 0: entered iff !(0 >= B) (scene.cu:147-152)
+                bool done = 0.0f >= B;
+                if (!done) {
+                    if (COUNT) pn++;
+                    if (ref & kLeaf) {
+                        leaf_range(S, ref, ti, te);
+                        done = ti == te;    // no triangles at all: spheres only
+                    }
+                }
+                if (done) {
+                    finish(slot);
+                    slot = -1;
+                }
+            }
+            wave_nonfinite = __ballot(slot >= 0 && !finite_inv) != 0;
+            if (root_internal && __ballot(fresh && slot >= 0)) {   // the fresh lanes' root step
+                bool need = false;
+                if (fresh && slot >= 0) need = node_step(ra, rb, rc, rk);
+                pop_loop(need);
+            }
+        }
+        if (!__ballot(slot >= 0)) {
+            if (exhausted) break;
+            continue;
+        }
+        if (slot < 0) continue;
+        // ---- one step: one triangle test of the current leaf, or one internal node; the record is read
+        // through the same loads either way (see trace_kernel)
+        bool need = false;
+        const bool in_leaf = ti < te;
+        const float4 *rec = in_leaf ? S.tris + (size_t)ti * 3 : S.nodes + (size_t)ref * 4;
+        const float4 a = rec[0], b = rec[1], c = rec[2];
+        uint2 kids = make_uint2(0, 0);
+        if (!in_leaf) kids = *reinterpret_cast<const uint2 *>(rec + 3);
+        if (in_leaf) {
+            if (COUNT) tt++;
+            float t;
+            const bool hit = ray_triangle_flat(o, d, v3(a.x, a.y, a.z), v3(a.w, b.x, b.y), v3(b.z, b.w, c.x), B, t);
+            if (hit) insert(t, S.sphere_count + ti);
+            ti++;
+            need = ti == te;
+        } else {
+            need = node_step(a, b, c, kids);
+        }
+        pop_loop(need);
+    }
+    if (slot <= -2) finish(-2 - slot);
+    Counters *cs = ctr + ((blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) & (kCtrSlots - 1));
+    const unsigned long long nh = wave_sum(nhit);
+    if (COUNT) {
+        const unsigned long long a = wave_sum(pn), b = wave_sum(iv), t = wave_sum(tt), s = wave_sum(stn);
+        if (lane_id() == 0) {
+            atomicAdd(&cs->pn, a);
+            atomicAdd(&cs->iv, b);
+            atomicAdd(&cs->tt, t);
+            atomicAdd(&cs->st, s);
+        }
+    }
+    if (lane_id() == 0 && nh) atomicAdd(&cs->hits, nh);
+}
+
 }  // namespace
 
 // Resident ray queries (rt_query_*): the resident scene, a stream for the host-pointer calls, and the
@@ -371,7 +635,7 @@ struct rt_query {
     SceneDev scene;
     hipStream_t stream = nullptr;     // the host-pointer calls' (and init's uploads')
     bool counters = false;            // rt_opts.collect_counters: the COUNT builds of the traversal kernels
-    int blocks = 0;                   // most workgroups either traversal kernel keeps resident
+    int blocks = 0;                   // most workgroups any of the traversal kernels keeps resident
     size_t cap = 0;                   // rays the scratch holds
     DevBuf<float4> geo;
     DevBuf<float2> hits;
@@ -384,9 +648,14 @@ struct rt_query {
     size_t host_hit_cap = 0;          // closest_hit_host's further staging: uv | normal | position, material
     DevBuf<float> s_hit;
     DevBuf<int32_t> s_mat;
+    // multi_hit: the list words of the output the caller left out (t or index, n*k each), and
+    // multi_hit_host's staging of t and index (n*k each) and count (n)
+    size_t list_cap = 0, host_list_cap = 0;
+    DevBuf<float> list_t, s_list_t;
+    DevBuf<int32_t> list_i, s_list_i, s_count;
     hipEvent_t last = nullptr;
     bool pending = false;             // `last` has been recorded
-    int last_kind = 0;                // 0 none (or an update), 1 closest, 2 occluded
+    int last_kind = 0;                // 0 none (or an update), 1 closest, 2 occluded, 3 multi_hit
     int32_t last_n = 0;
     rtamd::RefitPlan plan;            // rt_query_update_triangles: level tables, built in init
 
@@ -409,15 +678,16 @@ struct rt_query {
         HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         int rc = scene.init(sc, o->device, stream);
         if (rc) return rc;
-        int per_cu_c = 0, per_cu_a = 0;
+        int per_cu_c = 0, per_cu_a = 0, per_cu_m = 0;
         if ((rc = trace_closest_blocks_per_cu(per_cu_c))) return rc;
         HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_a, anyhit_kernel<false>, kBlock, 0));
-        blocks = std::max(1, scene.cus * std::max({1, per_cu_c, per_cu_a}));
+        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_m, multihit_kernel<false>, kBlock, 0));
+        blocks = std::max(1, scene.cus * std::max({1, per_cu_c, per_cu_a, per_cu_m}));
         HIPCHK(hipEventCreateWithFlags(&last, hipEventDisableTiming));
         if ((rc = words.alloc((size_t)(1 + kQueues) * kQueueStride))) return rc;
         if ((rc = plan.build(sc, scene.node_rec, stream))) return rc;
         // trace_kernel: 2 words (ref, distance) for each of kStackMax - kStackLds entries per lane; the
-        // any-hit kernel's kStackMax - kAnyStackLds one-word entries fit in the same buffer
+        // any-hit and multi-hit kernels' kStackMax - kAnyStackLds one-word entries fit in the same buffer
         return overflow.alloc((size_t)blocks * kBlock * 2 * (kStackMax - kStackLds));
     }
     int wait_last() {
@@ -482,6 +752,63 @@ struct rt_query {
             hipLaunchKernelGGL(anyhit_kernel<false>, dim3(grid), dim3(kBlock), 0, s, scene.ds, geo.p, live(), queue(), d_occ,
                                overflow.p, scene.ctr.p);
         return end(2, n, s);
+    }
+    // All hits before the bound, the k nearest kept.  The kernel keeps each ray's list in the
+    // caller's rows; an output the caller left out is replaced by the object's scratch when the other one is
+    // asked for, and with neither the kernel only counts.
+    int multi_hit(const float *d_rays, const float *d_tmax, int n, int k, const rt_multi_hit_out &out, hipStream_t s) {
+        float *lt = out.t;
+        int32_t *li = out.index;
+        if ((lt != nullptr) != (li != nullptr)) {
+            const size_t need = (size_t)n * k;
+            if (need > list_cap) {
+                HIPCHK(hipSetDevice(scene.device));
+                int rc = wait_last();       // the last call may still use the old lists
+                if (rc) return rc;
+                const size_t want = std::max(need, 2 * list_cap);
+                list_cap = 0;
+                if ((rc = list_t.alloc(want)) || (rc = list_i.alloc(want))) return rc;
+                list_cap = want;
+            }
+            if (!lt) lt = list_t.p;
+            if (!li) li = list_i.p;
+        }
+        int rc = begin(d_rays, d_tmax, n, s);
+        if (rc) return rc;
+        const int grid = std::min(blocks_for(n), blocks);
+        if (counters)
+            hipLaunchKernelGGL(multihit_kernel<true>, dim3(grid), dim3(kBlock), 0, s, scene.ds, geo.p, live(), queue(), k, lt,
+                               li, out.count, overflow.p, scene.ctr.p);
+        else
+            hipLaunchKernelGGL(multihit_kernel<false>, dim3(grid), dim3(kBlock), 0, s, scene.ds, geo.p, live(), queue(), k, lt,
+                               li, out.count, overflow.p, scene.ctr.p);
+        return end(3, n, s);
+    }
+    int multi_hit_host(const float *rays, const float *tmax, int n, int k, const rt_multi_hit_out &out) {
+        int rc = reserve_host(n);
+        if (rc) return rc;
+        const size_t m = (size_t)n * k;
+        if (m > host_list_cap) {
+            HIPCHK(hipSetDevice(scene.device));
+            const size_t want = std::max(m, 2 * host_list_cap);
+            host_list_cap = 0;              // the host calls are blocking: nothing reads the old staging
+            if ((rc = s_list_t.alloc(want)) || (rc = s_list_i.alloc(want))) return rc;
+            host_list_cap = want;
+        }
+        if (s_count.n < host_cap && (rc = s_count.alloc(host_cap))) return rc;
+        hipStream_t s = stream;
+        rt_multi_hit_out d{};
+        if (out.t) d.t = s_list_t.p;
+        if (out.index) d.index = s_list_i.p;
+        if (out.count) d.count = s_count.p;
+        HIPCHK(hipMemcpyAsync(s_rays.p, rays, (size_t)n * 6 * sizeof(float), hipMemcpyHostToDevice, s));
+        if (tmax) HIPCHK(hipMemcpyAsync(s_tmax.p, tmax, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s));
+        if ((rc = multi_hit(s_rays.p, tmax ? s_tmax.p : nullptr, n, k, d, s))) return rc;
+        if (out.t) HIPCHK(hipMemcpyAsync(out.t, d.t, m * sizeof(float), hipMemcpyDeviceToHost, s));
+        if (out.index) HIPCHK(hipMemcpyAsync(out.index, d.index, m * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        if (out.count) HIPCHK(hipMemcpyAsync(out.count, d.count, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return RT_OK;
     }
     int reserve_host(int n) {
         if ((size_t)n <= host_cap) return RT_OK;
@@ -692,6 +1019,34 @@ int rt_query_closest_hit_host(rt_query *q, const float *rays, int32_t n, const r
     if (n == 0) return RT_OK;
     if (!rays || !out) return rtamd::fail(RT_E_INVALID, "rt_query_closest_hit_host: null pointer");
     return q->closest_hit_host(rays, n, *out);
+}
+
+// The checks shared by the two multi-hit calls; > 0: n == 0, nothing to do.
+static int multi_hit_args(const char *fn, const rt_query *q, const void *rays, int32_t n, int32_t k, const void *out) {
+    const std::string f(fn);
+    if (!q) return rtamd::fail(RT_E_INVALID, f + ": null query object");
+    if (n < 0) return rtamd::fail(RT_E_INVALID, f + ": negative ray count");
+    if (k < 1 || k > RT_MULTI_HIT_MAX)
+        return rtamd::fail(RT_E_INVALID, f + ": k " + std::to_string(k) + " is outside 1.." + std::to_string(RT_MULTI_HIT_MAX));
+    if (n == 0) return 1;
+    if (!rays || !out) return rtamd::fail(RT_E_INVALID, f + ": null pointer");
+    if ((int64_t)n * k > INT32_MAX)
+        return rtamd::fail(RT_E_INVALID, f + ": n * k = " + std::to_string((int64_t)n * k) + " does not fit int32");
+    return RT_OK;
+}
+
+int rt_query_multi_hit(rt_query *q, const float *d_rays, const float *d_tmax, int32_t n, int32_t k,
+                       const rt_multi_hit_out *d_out, void *hip_stream) {
+    const int rc = multi_hit_args("rt_query_multi_hit", q, d_rays, n, k, d_out);
+    if (rc) return rc > 0 ? RT_OK : rc;
+    return q->multi_hit(d_rays, d_tmax, n, k, *d_out, static_cast<hipStream_t>(hip_stream));
+}
+
+int rt_query_multi_hit_host(rt_query *q, const float *rays, const float *tmax, int32_t n, int32_t k,
+                            const rt_multi_hit_out *out) {
+    const int rc = multi_hit_args("rt_query_multi_hit_host", q, rays, n, k, out);
+    if (rc) return rc > 0 ? RT_OK : rc;
+    return q->multi_hit_host(rays, tmax, n, k, *out);
 }
 
 int rt_query_stats(rt_query *q, rt_stats *stats) {

@@ -102,6 +102,31 @@ def _hit_fields(fields):
     return tuple(k for k in HIT_FIELDS if k in names)
 
 
+class RtMultiHitOut(C.Structure):
+    """rt_multi_hit_out: t (n x k), index (n x k), count (n); every pointer optional."""
+    _fields_ = [(n, P) for n in ("t", "index", "count")]
+
+
+MULTI_HIT_MAX = 64   # RT_MULTI_HIT_MAX
+
+
+def _multi_hit_k(k):
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise ValueError("k must be an integer, not %s" % type(k).__name__)
+    if not 1 <= int(k) <= MULTI_HIT_MAX:
+        raise ValueError("k must be in 1..%d, not %d" % (MULTI_HIT_MAX, int(k)))
+    return int(k)
+
+
+def _tmax_np(tmax, n):
+    if tmax is None:
+        return None
+    tm = np.asarray(tmax)
+    if tm.dtype != np.float32 or tm.shape != (n,) or not tm.flags["C_CONTIGUOUS"]:
+        raise ValueError("tmax must be a contiguous float32 array of shape (n,)")
+    return tm
+
+
 _lib = None
 
 
@@ -282,6 +307,21 @@ class Scene:
             out["front_face"] = out["front_face"].view(np.bool_)
         return {k: out[k] for k in names}
 
+    def multi_hit(self, rays, k, tmax=None):
+        """rt_scene_multi_hit: the host twin of RayQuery.multi_hit, no GPU: rays (n, 6) float32 and
+        tmax None or (n,) float32, numpy and contiguous.  Returns (t (n, k) float32, index (n, k) int32,
+        count (n,) int32), bit for bit what the device call writes."""
+        k = _multi_hit_k(k)
+        a = RayQuery._rays_np(rays)
+        n = a.shape[0]
+        tm = _tmax_np(tmax, n)
+        t, idx, cnt = np.zeros((n, k), np.float32), np.zeros((n, k), np.int32), np.zeros(n, np.int32)
+        mo = RtMultiHitOut(_ptr(t), _ptr(idx), _ptr(cnt))
+        f = lib().rt_scene_multi_hit
+        f.argtypes = [P, P, P, I32, I32, P]
+        _check(f(self.ptr, _ptr(a), _ptr(tm) if tm is not None else None, n, k, C.byref(mo)))
+        return t, idx, cnt
+
     def arrays(self):
         v = self.view
 
@@ -450,6 +490,7 @@ class RayQuery:
     (float32 t, int32 index, bool mask) and the work is enqueued on torch.cuda.current_stream(device)
     without any synchronisation: they are ready in stream order, like any torch op's.
     closest_hit(rays, fields=...) is closest with the hit record (uv, normal, position, material, front_face),
+    and multi_hit(rays, k, tmax=None) -> (t, index, count) the k nearest hits in order with the crossing count,
     under the same rules; update(vertices) moves the triangles under the frozen BVH topology."""
 
     def __init__(self, scene, device=0, counters=False, L=None):
@@ -575,6 +616,40 @@ class RayQuery:
         _check(self.L.rt_query_occluded_host(self.h, _ptr(a), _ptr(tm) if tm is not None else None, n, _ptr(occ)),
                self.L)
         return occ.view(np.bool_)
+
+    def multi_hit(self, rays, k, tmax=None):
+        """rt_query_multi_hit: every hit before tmax (per ray; None = 1e30), the k nearest kept in order
+        (DESIGN §14).  Returns (t (n, k) float32, index (n, k) int32, count (n,) int32): count is the number of
+        surfaces the ray crosses, not capped by k; row entries past min(count, k) are (1e30, -1).  1 <= k <= 64.
+        Tensors in, tensors out on torch.cuda.current_stream(device) without any synchronisation (tmax then a
+        tensor too); a numpy array takes the _host path (blocking) and gives numpy."""
+        k = _multi_hit_k(k)
+        f = self.L
+        if _is_tensor(rays):
+            import torch
+            n = self.check_tensor(rays, self.device)
+            if tmax is not None:
+                if not _is_tensor(tmax):
+                    raise ValueError("tmax must be a torch.Tensor when rays is one")
+                if self.check_tensor(tmax, self.device, "tmax", ()) != n:
+                    raise ValueError("tmax must have one entry per ray")
+            t = torch.empty((n, k), dtype=torch.float32, device=rays.device)
+            idx = torch.empty((n, k), dtype=torch.int32, device=rays.device)
+            cnt = torch.empty(n, dtype=torch.int32, device=rays.device)
+            mo = RtMultiHitOut(t.data_ptr(), idx.data_ptr(), cnt.data_ptr())
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            f.rt_query_multi_hit.argtypes = [P, P, P, I32, I32, P, P]
+            _check(f.rt_query_multi_hit(self.h, P(rays.data_ptr()), P(tmax.data_ptr()) if tmax is not None else None, n, k,
+                                        C.byref(mo), P(stream) if stream else None), f)
+            return t, idx, cnt
+        a = self._rays_np(rays)
+        n = a.shape[0]
+        tm = _tmax_np(tmax, n)
+        t, idx, cnt = np.zeros((n, k), np.float32), np.zeros((n, k), np.int32), np.zeros(n, np.int32)
+        mo = RtMultiHitOut(_ptr(t), _ptr(idx), _ptr(cnt))
+        f.rt_query_multi_hit_host.argtypes = [P, P, P, I32, I32, P]
+        _check(f.rt_query_multi_hit_host(self.h, _ptr(a), _ptr(tm) if tm is not None else None, n, k, C.byref(mo)), f)
+        return t, idx, cnt
 
     def update(self, vertices):
         """rt_query_update_triangles: new vertices (n, 9) float32 {a.xyz, b.xyz, c.xyz} in the scene's

@@ -409,6 +409,62 @@ int rt_query_closest_hit_host(rt_query *q, const float *rays, int32_t n, const r
 int rt_scene_hit_records(const rt_scene *scene, const float *rays, const float *t, const int32_t *index,
                          int32_t n, const rt_hit_out *out);
 
+/* Multi-hit queries: the K nearest hits of a ray, in order, and how many surfaces it crosses.  The
+ * presence of these symbols is the feature probe; RT_ABI_VERSION and every existing struct are unchanged.  No
+ * reference counterpart as an interface; every predicate restates the reference's traversal.
+ * For ray i the bound B is rt_query_occluded's: B = tmax[i] where tmax[i] <= 1e30, otherwise (larger, +inf, NaN,
+ * or a NULL tmax) 1e30.  H is the set of primitives the reference traversal accepts with `closest` held at B and
+ * never updated:
+ *   spheres      every sphere k is tested with closest = B (scene.cu:340-371); an accepted one contributes the
+ *                hit (the t that test returns, k).
+ *   root         entered iff !(0 >= B) (scene.cu:147-152).
+ *   leaf         in an entered leaf every triangle j of [child2, child1) is tested with closest = B
+ *                (scene.cu:160-195); an accepted one contributes (its t, sphere_count + j).
+ *   internal     a child is entered iff ray_aabb_intersection(child, tmax = B) (scene.cu:109-132) holds and
+ *                !(entry >= B).
+ *   no exit      nothing stops early.
+ * These are rt_query_occluded's predicates, which depend on (ray, B, primitive or node) alone: H is a fixed set,
+ * whatever order the nodes are visited in, and rt_query_occluded returns H != {}.
+ * Order: hits are sorted by the key (t', index) ascending.  t' is t's bit pattern as an unsigned integer, with
+ * every NaN replaced by the one pattern 0x7FC00000.  An accepted t is NaN or >= 0.005 (the accept test lets a NaN
+ * t through, as in the branchy form), so unsigned order is numeric order with the NaNs last; a NaN's sign and
+ * payload are the processor's and do not influence the order.  Equal t' (two NaNs included) are ordered by index.
+ * Outputs, for a caller-chosen k with 1 <= k <= RT_MULTI_HIT_MAX:
+ *   count[i]                        |H| as int32, not capped by k;
+ *   t[i*k + j], index[i*k + j]      the j-th smallest hit by the key, for j < min(|H|, k);
+ *                                   1e30 and -1 for j >= min(|H|, k) (rt_query_closest's miss convention).
+ * Every pointer of rt_multi_hit_out is optional (NULL = not written); with all three NULL the call only traverses
+ * and counts (rt_query_stats).
+ * Exact relations to the other calls: count >= 1 <=> rt_query_occluded with the same tmax; for B = 1e30,
+ * count >= 1 <=> rt_query_closest's index >= 0.  t[0] is NOT promised to be the closest call's t: the closest
+ * traversal's shrinking bound can prune a box that the fixed bound enters.
+ * rt_query_multi_hit follows every rule of rt_query_occluded and rt_query_closest_hit: pointers on q's device,
+ * enqueued on hip_stream, joins the event chain, allocates nothing once the scratch holds n rays (when exactly one
+ * of t and index is NULL, the other's n*k list words live in a scratch of the object that grows like the rest)
+ * and never waits on the host; d_out is a host struct of device pointers, read before the call returns; the
+ * geometry is the object's current resident geometry (rt_query_update_triangles).  n == 0 is RT_OK and touches no
+ * pointer; a null object, n < 0, k outside 1..RT_MULTI_HIT_MAX, a null d_rays or d_out with n > 0, or an n * k
+ * that does not fit int32 is RT_E_INVALID before any HIP call (k is checked before n: a bad k is refused for n == 0
+ * too).
+ * rt_query_stats after it: live_segments = n, hits = rays with count >= 1, misses = the rest, hits_sphere = 0;
+ * with collect_counters Pn/Iv/Tt and sphere_tests are the full traversal's -- no exit, so they do not depend on
+ * the order and are exact on every ray.
+ * The _host variant takes host pointers, stages through buffers of the object and blocks.  rt_scene_multi_hit is
+ * the host twin: the same on a host scene, no GPU, bit for bit the device's output; it refuses the same bad
+ * arguments. */
+#define RT_MULTI_HIT_MAX 64
+typedef struct {            /* every pointer optional: NULL = not written */
+    float   *t;             /* n x k */
+    int32_t *index;         /* n x k */
+    int32_t *count;         /* n     */
+} rt_multi_hit_out;
+int rt_query_multi_hit(rt_query *q, const float *d_rays, const float *d_tmax /* NULL = 1e30 */, int32_t n,
+                       int32_t k, const rt_multi_hit_out *d_out, void *hip_stream);
+int rt_query_multi_hit_host(rt_query *q, const float *rays, const float *tmax, int32_t n, int32_t k,
+                            const rt_multi_hit_out *out);
+int rt_scene_multi_hit(const rt_scene *scene, const float *rays, const float *tmax, int32_t n, int32_t k,
+                       const rt_multi_hit_out *out);
+
 /* Replaces the bloom block of main (raytracing.cu:356-393, kernels :21-74): high-pass
  * (luminance > threshold), clamped box blur of `radius` horizontally then vertically,
  * add back.  fb is a host W*H*3 buffer, updated in place. */
