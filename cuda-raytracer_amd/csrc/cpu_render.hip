@@ -20,6 +20,7 @@
 
 namespace rtamd {
 int fail(int code, const std::string &msg);
+int check_scene(const rt_scene *s);   // scene_dev.hip
 }
 
 using namespace rtd;
@@ -127,6 +128,7 @@ void parallel_chunks(int total, int threads, F &&body) {
 extern "C" int rt_cpu_render(const rt_scene *s, float *fb, int32_t threads, double *seconds) {
     const auto t0 = std::chrono::high_resolution_clock::now();
     if (!s || !fb) return rtamd::fail(RT_E_INVALID, "rt_cpu_render: null argument");
+    if (const int rc = rtamd::check_scene(s)) return rc;   // process() reads the sky map like the kernels do
     if (threads <= 0) threads = (int)std::max(1u, std::thread::hardware_concurrency());
     const int64_t pixels = (int64_t)s->width * s->height;
     if (pixels * 20 > 0x7fffffff) return rtamd::fail(RT_E_INVALID, "image too large");

@@ -68,6 +68,11 @@ int check_scene(const rt_scene *s) {
     if (s->bvh_node_count < 1 || !s->bvh) return fail(RT_E_INVALID, "scene has no BVH root");
     if (s->environment_map_width < 1 || s->environment_map_height < 1 || !s->environment_map)
         return fail(RT_E_INVALID, "scene has no environment map");
+    // sky_color keeps the reference's row stride of the map's height (scene.cu:389-391): texel ty * h + tx stays
+    // below w * h only for w >= h (1 x 2 already reads index 2 of 2)
+    if (s->environment_map_width < s->environment_map_height)
+        return fail(RT_E_INVALID, "environment map is taller than wide: the sky lookup's row stride is the map's "
+                                  "height, so it would read past the map's end");
     if ((s->sphere_count && !s->spheres) || (s->triangle_count && !s->triangles) || !s->materials ||
         (s->sphere_count + s->triangle_count && !s->material_indices))
         return fail(RT_E_INVALID, "scene array missing");

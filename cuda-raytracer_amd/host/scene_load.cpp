@@ -401,6 +401,10 @@ int rt_scene_load(const char *path, const rt_load_opts *opts_in, rt_scene_host *
             const int rc = load_pfm(resolve(opts.asset_root, t[1]), s->env, v.environment_map_width,
                                     v.environment_map_height);
             if (rc) return bad(rc);
+            // the sky lookup's row stride is the map's height (scene.cu:389-391; check_scene has the bound)
+            if (v.environment_map_width < v.environment_map_height)
+                return bad(fail(RT_E_INVALID, "environment map '" + t[1] + "' is taller than wide: the sky lookup's "
+                                              "row stride is the map's height, so it would read past the map's end"));
             have_env = true;
             if (!opts.quiet)
                 std::printf("Loaded environment map with size %d,%d\n", v.environment_map_width, v.environment_map_height);

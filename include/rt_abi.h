@@ -51,7 +51,10 @@ typedef struct {                                                                
 typedef struct { rt_vec3 min_bound, max_bound; int32_t child1, child2; } rt_bvh_node; /* scene.cuh:82 */
 
 /* Host view of a loaded scene; mirrors `struct Scene` (scene.cuh:102-152). All pointers are
- * borrowed host memory. */
+ * borrowed host memory.  environment_map holds width * height texels and must be at least as wide as
+ * tall: the sky lookup's row stride is the map's height (scene.cu:389-391), which stays inside the map
+ * only then; every call that renders an rt_scene or makes it resident refuses a taller map with
+ * RT_E_INVALID, as does rt_scene_load. */
 typedef struct {
     const rt_sphere *spheres;         int32_t sphere_count;
     const rt_triangle *triangles;     int32_t triangle_count;

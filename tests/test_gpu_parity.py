@@ -171,8 +171,11 @@ def test_fused_and_plain_reorder_bitexact(gpu, monkeypatch, scene, image, sort, 
 def test_home_indexed_radiance_bitexact(gpu, monkeypatch, scene, image, home):
     """Sort on with the fused bounce-0 reorder (round 5): a surviving ray's radiance lives at its home index (its
     bounce-1 slot), the replay writes bounce-0 emission there and home_of[ray id] for the accumulation; RTAMD_HOME=0
-    keeps acc[ray id].  cornell_plus has an emitter (radiance terms at bounce 0 and later, the read-modify-write
-    path), spheres runs the fused replay at every bounce; both forms equal the oracle bit for bit."""
+    keeps acc[ray id].  cornell_plus has an emitter (radiance terms at bounce 0 and later), spheres runs the fused
+    replay at every bounce; both forms equal the oracle bit for bit.  What these scenes do not reach: every
+    material with `emit` in them has black albedos, so a ray's one nonzero term comes in the step it dies and acc
+    is never read back (acc_holds is false in every lane).  The read-modify-write, kAccFlag's trip through the
+    reorder and the bounce-0 term left to the replay run in test_gpu_shade_scenes.py, on emitters that scatter."""
     monkeypatch.setenv("RTAMD_HOME", home)
     osc, psc = _pair(scene, image)
     ofb, ost = osc.render(sort=True)
