@@ -5,8 +5,12 @@
 // __host__ __device__ code in rt_device.h (ray_sphere, ray_triangle, slab), so the accepted set and every t
 // are the device kernel's bit for bit; the node array is the scene's own (rt_scene.bvh), walked with a plain
 // stack -- the set does not depend on the order.  The hits are then sorted by the key (t', index) of rt_abi.h.
+//
+// Also rt_scene_closest_point, the host twin of rt_query_closest_point: the pinned walk with the
+// shrinking bound, every value from closest_point_math.h, which the device kernel compiles too.
 #include "rt_abi.h"
 #include "rt_device.h"
+#include "closest_point_math.h"
 
 #include <algorithm>
 #include <cstring>
@@ -67,7 +71,89 @@ void all_hits(const rt_scene &s, V3 o, V3 d, float B, std::vector<Hit> &hits, st
     }
 }
 
+// rt_scene_closest_point's walk (rt_abi.h) for one finite point: closest_point_kernel's, over the
+// scene's own node array.  The stack holds (node, box2) pairs; the walk pushes at most one per level.
+struct Entry { int32_t node; float box2; };
+
+void nearest(const rt_scene &s, rt_vec3 p, float &best2, int32_t &best, std::vector<Entry> &stack) {
+    namespace cp = rtamd::cp;
+    for (int i = 0; i < s.sphere_count; i++) {
+        rt_vec3 w;
+        float len;
+        const float d2 = cp::sphere_dist2(p, s.spheres[i].center, s.spheres[i].radius, w, len);
+        if (cp::accepts(d2, i, best2, best)) { best2 = d2; best = i; }
+    }
+    if (0.0f > best2) return;
+    stack.clear();
+    int32_t n = 0;
+    while (true) {
+        const rt_bvh_node &nd = s.bvh[n];
+        bool descend = false;
+        if (nd.child2 <= nd.child1) {
+            for (int j = nd.child2; j < nd.child1; j++) {
+                const rt_triangle &tr = s.triangles[j];
+                const float d2 = cp::triangle(p, tr.p1, tr.p2p1, tr.p3p1).dist2;
+                if (cp::accepts(d2, s.sphere_count + j, best2, best)) { best2 = d2; best = s.sphere_count + j; }
+            }
+        } else {
+            const rt_bvh_node &c1 = s.bvh[nd.child1], &c2 = s.bvh[nd.child2];
+            const float a = cp::box2(p, c1.min_bound, c1.max_bound), b = cp::box2(p, c2.min_bound, c2.max_bound);
+            const bool e1 = !(a > best2), e2 = !(b > best2);
+            if (e1 || e2) {
+                const bool second = e2 && (!e1 || b < a);
+                if (e1 && e2) stack.push_back(second ? Entry{nd.child1, a} : Entry{nd.child2, b});
+                n = second ? nd.child2 : nd.child1;
+                descend = true;
+            }
+        }
+        if (descend) continue;
+        bool found = false;
+        while (!stack.empty() && !found) {
+            const Entry e = stack.back();
+            stack.pop_back();
+            if (!(e.box2 > best2)) { n = e.node; found = true; }
+        }
+        if (!found) return;
+    }
+}
+
 }  // namespace
+
+extern "C" int rt_scene_closest_point(const rt_scene *s, const float *points, const float *max_dist, int32_t n,
+                                      const rt_closest_point_out *out) {
+    namespace cp = rtamd::cp;
+    if (!s) return rtamd::fail(RT_E_INVALID, "rt_scene_closest_point: null scene");
+    if (n < 0) return rtamd::fail(RT_E_INVALID, "rt_scene_closest_point: negative point count");
+    if (n == 0) return RT_OK;
+    if (!points || !out) return rtamd::fail(RT_E_INVALID, "rt_scene_closest_point: null pointer");
+    if (s->bvh_node_count < 1 || !s->bvh) return rtamd::fail(RT_E_INVALID, "rt_scene_closest_point: scene has no BVH root");
+    std::vector<Entry> stack;
+    for (int32_t i = 0; i < n; i++) {
+        const rt_vec3 p = {points[(size_t)i * 3], points[(size_t)i * 3 + 1], points[(size_t)i * 3 + 2]};
+        float best2 = max_dist ? cp::bound2(max_dist[i]) : INFINITY;
+        int32_t best = INT32_MAX;
+        if (cp::finite3(p)) nearest(*s, p, best2, best, stack);
+        const bool hit = best != INT32_MAX;
+        cp::Near nr{0.0f, 0.0f, 0.0f, {0.0f, 0.0f, 0.0f}};
+        if (hit && best < s->sphere_count) {
+            nr = cp::sphere(p, s->spheres[best].center, s->spheres[best].radius);
+        } else if (hit) {
+            const rt_triangle &tr = s->triangles[best - s->sphere_count];
+            nr = cp::triangle(p, tr.p1, tr.p2p1, tr.p3p1);
+        }
+        if (out->distance) out->distance[i] = hit ? sqrtf(best2) : 1e30f;
+        if (out->index) out->index[i] = hit ? best : -1;
+        if (out->point) {
+            float *q = out->point + (size_t)i * 3;
+            q[0] = nr.point.x; q[1] = nr.point.y; q[2] = nr.point.z;
+        }
+        if (out->uv) {
+            out->uv[(size_t)i * 2] = nr.u;
+            out->uv[(size_t)i * 2 + 1] = nr.v;
+        }
+    }
+    return RT_OK;
+}
 
 extern "C" int rt_scene_multi_hit(const rt_scene *s, const float *rays, const float *tmax, int32_t n, int32_t k,
                                   const rt_multi_hit_out *out) {

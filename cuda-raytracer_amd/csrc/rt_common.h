@@ -214,4 +214,11 @@ int trace_closest_blocks_per_cu(int &per_cu);
 void launch_trace_closest(bool count, int grid, hipStream_t s, const DevScene &ds, const float4 *geo, const uint32_t *live,
                           uint32_t *queue, float2 *hits, uint32_t *overflow, Counters *ctr);
 
+// closest_point_kernel (closest_point.hip) for rt_query.hip: the ingest of n points into `geo`
+// (one float4 each) and the traversal, enqueued on s.
+int closest_point_blocks_per_cu(int &per_cu);
+void launch_closest_point(bool count, int n, int grid, hipStream_t s, const DevScene &ds, const float *d_points,
+                          const float *d_max_dist, float4 *geo, uint32_t *live, uint32_t *queue,
+                          const rt_closest_point_out &out, uint32_t *overflow, Counters *ctr);
+
 }  // namespace rtamd

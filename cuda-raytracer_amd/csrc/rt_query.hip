@@ -2,7 +2,7 @@
 // them: the ingest, egest, hit-record, any-hit and multi-hit kernels, the query object
 // and its C ABI.
 // The closest-hit traversal is the renderer's trace_kernel, compiled in rt_render.hip and launched through
-// rt_common.h; the refit of rt_query_update_triangles is bvh_refit.hip.
+// rt_common.h, as is the closest-point traversal of closest_point.hip; the refit of rt_query_update_triangles is bvh_refit.hip.
 #include "rt_common.h"
 #include "bvh_refit.h"
 #include "bvh_refit_math.h"
@@ -655,7 +655,7 @@ struct rt_query {
     DevBuf<int32_t> list_i, s_list_i, s_count;
     hipEvent_t last = nullptr;
     bool pending = false;             // `last` has been recorded
-    int last_kind = 0;                // 0 none (or an update), 1 closest, 2 occluded, 3 multi_hit
+    int last_kind = 0;                // 0 none (or an update), 1 closest, 2 occluded, 3 multi_hit, 4 closest_point
     int32_t last_n = 0;
     rtamd::RefitPlan plan;            // rt_query_update_triangles: level tables, built in init
 
@@ -678,11 +678,11 @@ struct rt_query {
         HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         int rc = scene.init(sc, o->device, stream);
         if (rc) return rc;
-        int per_cu_c = 0, per_cu_a = 0, per_cu_m = 0;
-        if ((rc = trace_closest_blocks_per_cu(per_cu_c))) return rc;
+        int per_cu_c = 0, per_cu_a = 0, per_cu_m = 0, per_cu_p = 0;
+        if ((rc = trace_closest_blocks_per_cu(per_cu_c)) || (rc = closest_point_blocks_per_cu(per_cu_p))) return rc;
         HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_a, anyhit_kernel<false>, kBlock, 0));
         HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_m, multihit_kernel<false>, kBlock, 0));
-        blocks = std::max(1, scene.cus * std::max({1, per_cu_c, per_cu_a, per_cu_m}));
+        blocks = std::max(1, scene.cus * std::max({1, per_cu_c, per_cu_a, per_cu_m, per_cu_p}));
         HIPCHK(hipEventCreateWithFlags(&last, hipEventDisableTiming));
         if ((rc = words.alloc((size_t)(1 + kQueues) * kQueueStride))) return rc;
         if ((rc = plan.build(sc, scene.node_rec, stream))) return rc;
@@ -807,6 +807,37 @@ struct rt_query {
         if (out.t) HIPCHK(hipMemcpyAsync(out.t, d.t, m * sizeof(float), hipMemcpyDeviceToHost, s));
         if (out.index) HIPCHK(hipMemcpyAsync(out.index, d.index, m * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         if (out.count) HIPCHK(hipMemcpyAsync(out.count, d.count, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return RT_OK;
+    }
+    // The nearest surface point of each point: closest_point.hip's ingest and traversal in the
+    // scratch of the ray queries (one float4 slot per point, the same queue words and overflow buffer).
+    int closest_point(const float *d_points, const float *d_max_dist, int n, const rt_closest_point_out &out, hipStream_t s) {
+        HIPCHK(hipSetDevice(scene.device));
+        int rc = reserve(n);
+        if (rc) return rc;
+        if (pending) HIPCHK(hipStreamWaitEvent(s, last, 0));
+        launch_closest_point(counters, n, std::min(blocks_for(n), blocks), s, scene.ds, d_points, d_max_dist, geo.p, live(),
+                             queue(), out, overflow.p, scene.ctr.p);
+        return end(4, n, s);
+    }
+    int closest_point_host(const float *points, const float *max_dist, int n, const rt_closest_point_out &out) {
+        int rc = reserve_host_hit(n);
+        if (rc) return rc;
+        hipStream_t s = stream;
+        rt_closest_point_out d{};
+        if (out.distance) d.distance = s_t.p;
+        if (out.index) d.index = s_index.p;
+        if (out.uv) d.uv = s_hit.p;
+        if (out.point) d.point = s_hit.p + 2 * host_hit_cap;
+        HIPCHK(hipMemcpyAsync(s_rays.p, points, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, s));
+        if (max_dist) HIPCHK(hipMemcpyAsync(s_tmax.p, max_dist, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s));
+        if ((rc = closest_point(s_rays.p, max_dist ? s_tmax.p : nullptr, n, d, s))) return rc;
+        const size_t m = (size_t)n;
+        if (out.distance) HIPCHK(hipMemcpyAsync(out.distance, d.distance, m * sizeof(float), hipMemcpyDeviceToHost, s));
+        if (out.index) HIPCHK(hipMemcpyAsync(out.index, d.index, m * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        if (out.uv) HIPCHK(hipMemcpyAsync(out.uv, d.uv, m * 2 * sizeof(float), hipMemcpyDeviceToHost, s));
+        if (out.point) HIPCHK(hipMemcpyAsync(out.point, d.point, m * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         return RT_OK;
     }
@@ -1047,6 +1078,30 @@ int rt_query_multi_hit_host(rt_query *q, const float *rays, const float *tmax, i
     const int rc = multi_hit_args("rt_query_multi_hit_host", q, rays, n, k, out);
     if (rc) return rc > 0 ? RT_OK : rc;
     return q->multi_hit_host(rays, tmax, n, k, *out);
+}
+
+// The checks shared by the two closest-point calls; > 0: n == 0, nothing to do.
+static int closest_point_args(const char *fn, const rt_query *q, const void *points, int32_t n, const void *out) {
+    const std::string f(fn);
+    if (!q) return rtamd::fail(RT_E_INVALID, f + ": null query object");
+    if (n < 0) return rtamd::fail(RT_E_INVALID, f + ": negative point count");
+    if (n == 0) return 1;
+    if (!points || !out) return rtamd::fail(RT_E_INVALID, f + ": null pointer");
+    return RT_OK;
+}
+
+int rt_query_closest_point(rt_query *q, const float *d_points, const float *d_max_dist, int32_t n,
+                           const rt_closest_point_out *d_out, void *hip_stream) {
+    const int rc = closest_point_args("rt_query_closest_point", q, d_points, n, d_out);
+    if (rc) return rc > 0 ? RT_OK : rc;
+    return q->closest_point(d_points, d_max_dist, n, *d_out, static_cast<hipStream_t>(hip_stream));
+}
+
+int rt_query_closest_point_host(rt_query *q, const float *points, const float *max_dist, int32_t n,
+                                const rt_closest_point_out *out) {
+    const int rc = closest_point_args("rt_query_closest_point_host", q, points, n, out);
+    if (rc) return rc > 0 ? RT_OK : rc;
+    return q->closest_point_host(points, max_dist, n, *out);
 }
 
 int rt_query_stats(rt_query *q, rt_stats *stats) {

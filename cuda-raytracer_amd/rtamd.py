@@ -118,6 +118,45 @@ def _multi_hit_k(k):
     return int(k)
 
 
+class RtClosestPointOut(C.Structure):
+    """rt_closest_point_out: distance (n), index (n), point (n x 3), uv (n x 2); every pointer optional."""
+    _fields_ = [(n, P) for n in ("distance", "index", "point", "uv")]
+
+
+CLOSEST_POINT_FIELDS = tuple(n for n, _ in RtClosestPointOut._fields_)
+CLOSEST_POINT_SHAPES = {"distance": ((), np.float32), "index": ((), np.int32), "point": ((3,), np.float32),
+                        "uv": ((2,), np.float32)}
+
+
+def _closest_point_fields(fields):
+    """The requested closest-point fields in CLOSEST_POINT_FIELDS order; an unknown name raises ValueError."""
+    names = (fields,) if isinstance(fields, str) else tuple(fields)
+    for k in names:
+        if k not in CLOSEST_POINT_SHAPES:
+            raise ValueError("unknown closest-point field %r (known: %s)" % (k, ", ".join(CLOSEST_POINT_FIELDS)))
+    return tuple(k for k in CLOSEST_POINT_FIELDS if k in names)
+
+
+def _points_np(points):
+    a = np.asarray(points)
+    if a.dtype != np.float32:
+        raise ValueError("points must be float32, not %s" % a.dtype)
+    if a.ndim != 2 or a.shape[1] != 3:
+        raise ValueError("points must have shape (n, 3), not %s" % (a.shape,))
+    if not a.flags["C_CONTIGUOUS"]:
+        raise ValueError("points must be contiguous")
+    return a
+
+
+def _max_dist_np(max_dist, n):
+    if max_dist is None:
+        return None
+    md = np.asarray(max_dist)
+    if md.dtype != np.float32 or md.shape != (n,) or not md.flags["C_CONTIGUOUS"]:
+        raise ValueError("max_dist must be a contiguous float32 array of shape (n,)")
+    return md
+
+
 def _tmax_np(tmax, n):
     if tmax is None:
         return None
@@ -322,6 +361,26 @@ class Scene:
         _check(f(self.ptr, _ptr(a), _ptr(tm) if tm is not None else None, n, k, C.byref(mo)))
         return t, idx, cnt
 
+    def closest_point(self, points, max_dist=None, fields=CLOSEST_POINT_FIELDS):
+        """rt_scene_closest_point: the host twin of RayQuery.closest_point, no GPU: points (n, 3) float32
+        and max_dist None or (n,) float32, numpy and contiguous.  Returns a dict of the requested fields, bit for
+        bit what the device call writes."""
+        names = _closest_point_fields(fields)
+        a = _points_np(points)
+        n = a.shape[0]
+        md = _max_dist_np(max_dist, n)
+        out = {k: np.zeros((n,) + CLOSEST_POINT_SHAPES[k][0], CLOSEST_POINT_SHAPES[k][1]) for k in names}
+        co = RtClosestPointOut(**{k: _ptr(v) for k, v in out.items()})
+        f = lib().rt_scene_closest_point
+        f.argtypes = [P, P, P, I32, P]
+        _check(f(self.ptr, _ptr(a), _ptr(md) if md is not None else None, n, C.byref(co)))
+        return out
+
+    def signed_distance(self, points, direction=(0.5773503, 0.5773503, 0.5773503)):
+        """The host twin of RayQuery.signed_distance (numpy only): the same composition of closest_point and the
+        count-only multi_hit on this host scene, no GPU."""
+        return _signed_distance(self, points, direction)
+
     def arrays(self):
         v = self.view
 
@@ -480,6 +539,23 @@ def _is_tensor(x):
     return t.__module__.split(".")[0] == "torch" and hasattr(x, "data_ptr") and hasattr(x, "is_contiguous")
 
 
+def _signed_distance(obj, points, direction):
+    """signed_distance of a RayQuery or a Scene: closest_point's distance, negated where the count-only multi_hit
+    along `direction` is odd."""
+    d = np.asarray(direction, np.float32)
+    if d.shape != (3,):
+        raise ValueError("direction must have 3 components, not shape %s" % (d.shape,))
+    dist = obj.closest_point(points, fields=("distance",))["distance"]
+    if _is_tensor(points):
+        import torch
+        rays = torch.cat([points, torch.from_numpy(d).to(points.device).expand(points.shape[0], 3)], 1).contiguous()
+        odd = (obj.multi_hit(rays, 1)[2] & 1).bool()
+        return torch.where(odd, -dist, dist)
+    rays = np.ascontiguousarray(np.hstack([_points_np(points), np.tile(d, (dist.shape[0], 1))]), np.float32)
+    odd = (obj.multi_hit(rays, 1)[2] & 1).astype(bool)
+    return np.where(odd, -dist, dist).astype(np.float32)
+
+
 class RayQuery:
     """rt_query: resident ray queries (scene + BVH in HBM, scratch kept between calls).
 
@@ -491,7 +567,9 @@ class RayQuery:
     without any synchronisation: they are ready in stream order, like any torch op's.
     closest_hit(rays, fields=...) is closest with the hit record (uv, normal, position, material, front_face),
     and multi_hit(rays, k, tmax=None) -> (t, index, count) the k nearest hits in order with the crossing count,
-    under the same rules; update(vertices) moves the triangles under the frozen BVH topology."""
+    under the same rules; closest_point(points, max_dist=None) is the point query (nearest surface point, distance,
+    index, uv) and signed_distance its composition with the crossing parity; update(vertices) moves the triangles under
+    the frozen BVH topology."""
 
     def __init__(self, scene, device=0, counters=False, L=None):
         self.L = L or lib()
@@ -650,6 +728,54 @@ class RayQuery:
         f.rt_query_multi_hit_host.argtypes = [P, P, P, I32, I32, P]
         _check(f.rt_query_multi_hit_host(self.h, _ptr(a), _ptr(tm) if tm is not None else None, n, k, C.byref(mo)), f)
         return t, idx, cnt
+
+    def closest_point(self, points, max_dist=None, fields=CLOSEST_POINT_FIELDS):
+        """rt_query_closest_point: for each point the nearest surface point within max_dist (per point, inclusive;
+        None = unbounded) on the resident geometry.  Returns a dict of the requested fields: distance
+        (n,) float32 (1e30 on a miss), index (n,) int32 (spheres first, then sphere_count + triangle; -1 on a miss),
+        point (n, 3) and uv (n, 2) float32 (the point lies at p1 + u e1 + v e2 of the triangle; zeros on a miss and
+        (0, 0) on a sphere).  Fields that are not requested are neither computed into memory nor allocated;
+        fields=() only traverses and counts.  points (n, 3) float32, contiguous: a torch.Tensor on cuda:<device>
+        (max_dist then a tensor too) gives tensors on torch.cuda.current_stream(device) without any synchronisation;
+        a numpy array takes the _host path (blocking) and gives numpy.  Anything else raises ValueError."""
+        names = _closest_point_fields(fields)
+        f = self.L
+        if _is_tensor(points):
+            import torch
+            n = self.check_tensor(points, self.device, "points", shape_tail=(3,))
+            if max_dist is not None:
+                if not _is_tensor(max_dist):
+                    raise ValueError("max_dist must be a torch.Tensor when points is one")
+                if self.check_tensor(max_dist, self.device, "max_dist", ()) != n:
+                    raise ValueError("max_dist must have one entry per point")
+            dt = {np.float32: torch.float32, np.int32: torch.int32}
+            out = {k: torch.empty((n,) + CLOSEST_POINT_SHAPES[k][0], dtype=dt[CLOSEST_POINT_SHAPES[k][1]],
+                                  device=points.device) for k in names}
+            co = RtClosestPointOut(**{k: v.data_ptr() for k, v in out.items()})
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            f.rt_query_closest_point.argtypes = [P, P, P, I32, P, P]
+            _check(f.rt_query_closest_point(self.h, P(points.data_ptr()),
+                                            P(max_dist.data_ptr()) if max_dist is not None else None, n, C.byref(co),
+                                            P(stream) if stream else None), f)
+            return out
+        a = _points_np(points)
+        n = a.shape[0]
+        md = _max_dist_np(max_dist, n)
+        out = {k: np.zeros((n,) + CLOSEST_POINT_SHAPES[k][0], CLOSEST_POINT_SHAPES[k][1]) for k in names}
+        co = RtClosestPointOut(**{k: _ptr(v) for k, v in out.items()})
+        f.rt_query_closest_point_host.argtypes = [P, P, P, I32, P]
+        _check(f.rt_query_closest_point_host(self.h, _ptr(a), _ptr(md) if md is not None else None, n, C.byref(co)), f)
+        return out
+
+    def signed_distance(self, points, direction=(0.5773503, 0.5773503, 0.5773503)):
+        """closest_point's distance, negated where the point lies inside a closed mesh: a point is taken to be inside
+        where the ray from it along `direction` (unit length) crosses an odd number of surfaces (the count-only
+        multi_hit).  A composition of the two queries, Python only.  It is a parity test: a ray that grazes an
+        edge or a vertex of the mesh, or runs inside a face's plane, can count a crossing twice or not at all and
+        flip the sign, and an open mesh has no inside; hits nearer than 0.005 along the ray are not counted, as
+        everywhere.  Misses of closest_point (non-finite points) keep 1e30.  points as for closest_point; returns a
+        tensor or an array like it."""
+        return _signed_distance(self, points, direction)
 
     def update(self, vertices):
         """rt_query_update_triangles: new vertices (n, 9) float32 {a.xyz, b.xyz, c.xyz} in the scene's

@@ -468,6 +468,78 @@ int rt_query_multi_hit_host(rt_query *q, const float *rays, const float *tmax, i
 int rt_scene_multi_hit(const rt_scene *scene, const float *rays, const float *tmax, int32_t n, int32_t k,
                        const rt_multi_hit_out *out);
 
+/* Closest-point queries: for a point, the nearest surface point, its distance and the primitive.  The
+ * presence of these symbols is the feature probe; RT_ABI_VERSION and every existing struct are unchanged.  No
+ * reference counterpart (the reference answers ray queries only).
+ * All arithmetic is float32, each operation rounded once, no contraction; dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z.
+ * points = n x {x y z} floats, contiguous; max_dist = n floats or NULL (unbounded).  S = the scene's sphere count.
+ *   bound        for max_dist R: B2 = R*R if 0 <= R <= 1e18; B2 = -1 (nothing qualifies) if R < 0; otherwise (larger,
+ *                +inf, NaN, or a NULL max_dist) B2 = +inf.  A point with a non-finite component is a miss and nothing
+ *                is traversed (no sphere is tested either).
+ *   triangle     record (p1, e1 = p2p1, e2 = p3p1), query point p: Ericson's region test on the record's own edges.
+ *                  ap = p - p1;  bp = ap - e1;  cp = ap - e2
+ *                  d1 = dot(e1,ap) d2 = dot(e2,ap) d3 = dot(e1,bp) d4 = dot(e2,bp) d5 = dot(e1,cp) d6 = dot(e2,cp)
+ *                  vc = d1*d4 - d3*d2;  vb = d5*d2 - d1*d6;  va = d3*d6 - d5*d4
+ *                (u, v) is the first of these that applies:
+ *                  A     d1 <= 0 && d2 <= 0                      (0, 0)
+ *                  B     d3 >= 0 && d4 <= d3                     (1, 0)
+ *                  AB    vc <= 0 && d1 >= 0 && d3 <= 0           (d1 / (d1 - d3), 0)
+ *                  C     d6 >= 0 && d5 <= d6                     (0, 1)
+ *                  AC    vb <= 0 && d2 >= 0 && d6 <= 0           (0, d2 / (d2 - d6))
+ *                  BC    va <= 0 && d4 - d3 >= 0 && d5 - d6 >= 0 w = (d4 - d3) / ((d4 - d3) + (d5 - d6)); (1 - w, w)
+ *                  face  otherwise                               den = 1 / ((va + vb) + vc); (vb * den, vc * den)
+ *                point = (p1 + u*e1) + v*e2 per component; dist2 = dot(p - point, p - point).  uv means what it
+ *                means in hit records: the point lies at p1 + u e1 + v e2.  A NaN dist2 (a zero-area triangle, for
+ *                example) is never accepted.
+ *   sphere       (c, r): w = p - c; len = sqrtf(dot(w, w)); g = len - r; dist2 = g*g; point = c + (r / len) * w per
+ *                component, and c + (r, 0, 0) for len == 0; uv = (+0, +0).
+ *   box          node box (lo, hi): per axis q = fmaxf(fmaxf(lo - p, p - hi), 0); box2 = (qx*qx + qy*qy) + qz*qz.
+ * The walk.  The bound shrinks as primitives are accepted, so the visit order is part of the definition (as it is for
+ * rt_query_closest, and unlike rt_query_occluded and rt_query_multi_hit, whose bound is fixed).  State (best2, best) =
+ * (B2, INT32_MAX); the primitive with index i at dist2 is accepted, and becomes the state, iff
+ * dist2 < best2 || (dist2 == best2 && i < best).
+ *   1. spheres 0..S-1 in order (index k);
+ *   2. if 0 > best2 stop, otherwise enter the root;
+ *   3. leaf: its triangles [child2, child1) in order (index S + j), then pop;
+ *   4. internal node: a = box2(child1), b = box2(child2); a child is eligible iff !(box2 > best2); child2 goes first
+ *      iff it is eligible and (child1 is not, or b < a) -- a tie goes to child1; enter the first child and push the
+ *      other one with its box2 if it is eligible too; with neither eligible, pop;
+ *   5. pop: discard entries whose stored box2 > best2 (tested against the current state), enter the first that
+ *      survives; an empty stack ends the query.
+ * Outputs (rt_closest_point_out; every pointer optional, NULL = not written, all NULL = only traverse and count):
+ *   distance[i] = sqrtf(best2), index[i] = best, point[i*3..], uv[i*2..] = those of the accepted primitive, evaluated
+ *   once more by the same functions; a miss (nothing accepted) gives 1e30, -1, (+0, +0, +0), (+0, +0).  max_dist is
+ *   inclusive: a primitive at exactly dist2 == B2 is accepted.
+ * Relation to the unpruned minimum: the result is the minimum of the key (dist2, index) over the primitives the walk
+ * tests, which is >= the minimum over all primitives under the same functions.  The two are equal unless a node's
+ * float box2 exceeds the float dist2 of a triangle inside that box by rounding -- box2 and dist2 are rounded
+ * independently, so that is possible, and the walk then prunes the box; the answer is then farther than the true
+ * nearest point by rounding error only (DESIGN §15 has the measured bound).
+ * rt_query_closest_point follows every rule of rt_query_multi_hit: pointers on q's device, enqueued on hip_stream,
+ * joins the event chain, allocates nothing once the scratch holds n points (rt_query_reserve counts points like rays)
+ * and never waits on the host; d_out is a host struct of device pointers, read before the call returns; the geometry
+ * is the object's current resident geometry (rt_query_update_triangles).  n == 0 is RT_OK and touches no pointer; a
+ * null object, n < 0, or a null d_points or d_out with n > 0 is RT_E_INVALID before any HIP call.
+ * rt_query_stats after it: live_segments = n, hits = queries with index >= 0, misses = the rest, hits_sphere = those
+ * whose nearest primitive is a sphere; with collect_counters Pn = nodes entered (the root, each child entered, each
+ * popped entry that survives), Iv = internal nodes visited, Tt = triangle tests, and sphere_tests -- all exact,
+ * because the order is pinned.
+ * The _host variant takes host pointers, stages through buffers of the object and blocks.  rt_scene_closest_point is
+ * the host twin: the same walk over rt_scene.bvh on a host scene, no GPU, bit for bit the device's output (or NaN on
+ * both sides); it refuses the same bad arguments. */
+typedef struct {            /* every pointer optional: NULL = not written */
+    float   *distance;      /* n     */
+    int32_t *index;         /* n     */
+    float   *point;         /* n x 3 */
+    float   *uv;            /* n x 2 */
+} rt_closest_point_out;
+int rt_query_closest_point(rt_query *q, const float *d_points, const float *d_max_dist /* NULL = unbounded */,
+                           int32_t n, const rt_closest_point_out *d_out, void *hip_stream);
+int rt_query_closest_point_host(rt_query *q, const float *points, const float *max_dist, int32_t n,
+                                const rt_closest_point_out *out);
+int rt_scene_closest_point(const rt_scene *scene, const float *points, const float *max_dist, int32_t n,
+                           const rt_closest_point_out *out);
+
 /* Replaces the bloom block of main (raytracing.cu:356-393, kernels :21-74): high-pass
  * (luminance > threshold), clamped box blur of `radius` horizontally then vertically,
  * add back.  fb is a host W*H*3 buffer, updated in place. */
