@@ -191,12 +191,15 @@ __device__ __forceinline__ V3 primary_dir(const DevScene &S, int i, const PassAr
 // as soon as that lane's ray is done, so incoherent rays of very different traversal lengths
 // do not leave most lanes idle.  Output per slot: {closest t, hit index} (index -1 = miss).
 // The slab pair, the flat triangle test and the leaf refs are rt_common.h's (shared with anyhit_kernel).
-template <bool SORTED, bool COUNT, int FIRST>
+// VSLOT (bounce 1 of the virtual reorder, below): the launch walks every slot of the pass, slot = ray id, and a
+// slot whose bounce-0 bucket (slot_bkt) is kDead is dropped at refill, before anything is counted.
+template <bool SORTED, bool COUNT, int FIRST, bool VSLOT = false>
 __global__ __launch_bounds__(kBlock) RT_TRACE_ATTR void trace_kernel(DevScene S, PassArgs pa, const float4 *__restrict__ geo,
                                                        const uint32_t *__restrict__ live_count,
                                                        uint32_t *__restrict__ queue, float2 *__restrict__ hits,
                                                        uint32_t *__restrict__ overflow, Counters *__restrict__ ctr,
-                                                       unsigned long long *__restrict__ tspan) {
+                                                       unsigned long long *__restrict__ tspan,
+                                                       const uint8_t *__restrict__ slot_bkt = nullptr) {
     __shared__ uint2 stack[(kStackLds + 1) * kBlock];   // + one scratch entry per lane
     // tspan (per-launch timing, rt_renderer_set_event_timing): {first wave start, last wave end}
     // on the device's constant-rate wall clock, so a launch's duration excludes the queueing
@@ -350,29 +353,37 @@ __global__ __launch_bounds__(kBlock) RT_TRACE_ATTR void trace_kernel(DevScene S,
                 slot = -1;
             }
             bool fresh = false;
-            while (idle && !exhausted) {
-                if (q_next >= q_end) {
-                    const uint32_t seg_lo = (uint32_t)(((uint64_t)L * shard) / kQueues);
-                    const uint32_t seg_hi = (uint32_t)(((uint64_t)L * (shard + 1)) / kQueues);
-                    uint32_t c = 0;
-                    if (lane_id() == 0) c = atomicAdd(queue + shard * kQueueStride, chunk);
-                    c = __builtin_amdgcn_readfirstlane(__shfl(c, 0)) + seg_lo;
-                    if (c >= seg_hi) {
-                        shard = (shard + 1) % kQueues;
-                        if (++tried == kQueues) exhausted = true;
-                        continue;
+            // one turn hands slots to the idle lanes; VSLOT takes further turns while lanes drew dead slots
+            do {
+                bool got = false;       // VSLOT: the lane took a slot in this turn
+                while (idle && !exhausted) {
+                    if (q_next >= q_end) {
+                        const uint32_t seg_lo = (uint32_t)(((uint64_t)L * shard) / kQueues);
+                        const uint32_t seg_hi = (uint32_t)(((uint64_t)L * (shard + 1)) / kQueues);
+                        uint32_t c = 0;
+                        if (lane_id() == 0) c = atomicAdd(queue + shard * kQueueStride, chunk);
+                        c = __builtin_amdgcn_readfirstlane(__shfl(c, 0)) + seg_lo;
+                        if (c >= seg_hi) {
+                            shard = (shard + 1) % kQueues;
+                            if (++tried == kQueues) exhausted = true;
+                            continue;
+                        }
+                        q_next = c;
+                        q_end = min(c + chunk, seg_hi);
                     }
-                    q_next = c;
-                    q_end = min(c + chunk, seg_hi);
+                    const uint32_t avail = q_end - q_next;
+                    const uint32_t r = rank_below(idle);
+                    const bool take = slot < 0 && r < avail;
+                    const unsigned long long took = __ballot(take);
+                    if (take) { slot = (int)(q_next + r); fresh = true; got = true; }
+                    q_next += (uint32_t)__popcll(took);
+                    idle &= ~took;
                 }
-                const uint32_t avail = q_end - q_next;
-                const uint32_t r = rank_below(idle);
-                const bool take = slot < 0 && r < avail;
-                const unsigned long long took = __ballot(take);
-                if (take) { slot = (int)(q_next + r); fresh = true; }
-                q_next += (uint32_t)__popcll(took);
-                idle &= ~took;
-            }
+                if (VSLOT) {            // a ray that ended at bounce 0: the lane takes another slot
+                    if (got && slot_bkt[slot] == kDead) { slot = -1; fresh = false; }
+                    idle = __ballot(slot < 0);
+                }
+            } while (VSLOT && idle && !exhausted);
             if (fresh) {
                 {
                     nlive++;
@@ -1145,6 +1156,116 @@ __global__ __launch_bounds__(kBlock) RT_REPLAY_ATTR void sort_scatter_shade_kern
     }
 }
 
+// ---------------------------------------------------------------- virtual bounce-0 reorder
+// Sort on, untiled, a scene with triangles (rt_renderer::vre): the bounce-0 reorder moves nothing.  The reference's
+// sorted position matters to a ray only as the seed of its next shading, and only the rays alive at bounce 2 need
+// to stand in that order.  So bounce 0 shades once in place (shade_kernel, not FUSED: state, bucket, histogram, rid
+// with kAccFlag, all in ray-id order) and sort_scan_kernel gives the bucket runs; bounce 1 traces over the ray-id
+// slots (trace_kernel<.., VSLOT>) and shade_rank_kernel computes each live slot's sorted position with the
+// scatter's own ranking, shades with that position as the seed, and moves only the survivors of bounce 1, to their
+// sorted positions of the other buffer set.  The positions of the rays that ended at bounce 1 stay kDead holes of
+// the bounce-1 bucket array (fill_dead_kernel), which the plain reorder that follows drops.
+
+// The bucket bytes [0, *count) = kDead.
+__global__ __launch_bounds__(kBlock) void fill_dead_kernel(uint8_t *__restrict__ bkt, const uint32_t *__restrict__ count) {
+    const uint32_t n = *count;
+    const uint32_t n16 = n / 16;        // 16-B stores for the bulk (the buffer is hipMalloc-aligned)
+    const uint32_t w = kDead * 0x01010101u;
+    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n16; i += gridDim.x * kBlock)
+        reinterpret_cast<uint4 *>(bkt)[i] = make_uint4(w, w, w, w);
+    for (uint32_t i = n16 * 16 + blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) bkt[i] = (uint8_t)kDead;
+}
+
+// Bounce 1 over the ray-id slots [0, *slot_count): the tiles and rounds of the bounce-0 histogram, the ranking of
+// sort_scatter_kernel on the bounce-0 buckets, shade_kernel's shading and radiance rules with seed = the sorted
+// position.  acc is indexed by ray id = slot, so a terminating ray's add is coalesced.
+template <bool COUNT>
+__global__ __launch_bounds__(kBlock) RT_SHADE_ATTR void shade_rank_kernel(DevScene S, PassArgs pa,
+                                                            const uint8_t *__restrict__ bkt_in,
+                                                            const float4 *__restrict__ geo_in,
+                                                            const float *__restrict__ tz_in,
+                                                            const uint32_t *__restrict__ rid_in,
+                                                            const float2 *__restrict__ hits, uint32_t seed_term, int last,
+                                                            const uint32_t *__restrict__ slot_count, int tiles,
+                                                            const uint32_t *__restrict__ offsets,
+                                                            const uint32_t *__restrict__ totals,
+                                                            float4 *__restrict__ geo_out, float *__restrict__ tz_out,
+                                                            uint32_t *__restrict__ rid_out, uint8_t *__restrict__ bkt_out,
+                                                            float4 *__restrict__ acc, Counters *__restrict__ ctr) {
+    const int n = (int)__builtin_amdgcn_readfirstlane(*slot_count);
+    __shared__ uint32_t run[kBuckets];
+    __shared__ uint32_t wcount[kBlock / 64][kBuckets];
+    unsigned hit = 0, miss = 0, hit_sphere = 0;
+    const int R = tile_rounds(n), span = kBlock * R;
+    for (int tile = blockIdx.x; tile * span < n; tile += gridDim.x) {
+        bucket_runs(run, offsets, totals, tiles, tile);
+        for (int k = threadIdx.x; k < (kBlock / 64) * kBuckets; k += kBlock) (&wcount[0][0])[k] = 0;
+        __syncthreads();
+        const int wave = threadIdx.x >> 6;
+        const int base = tile * span;
+        const int rounds = min(R, (n - base + kBlock - 1) / kBlock);   // block-uniform: the last tile is short
+        for (int r = 0; r < rounds; r++) {
+            const int item = base + r * kBlock + threadIdx.x;
+            const bool valid = item < n;
+            const uint32_t b = valid ? bkt_in[item] : 0u;
+            const bool move = valid && b != kDead;
+            ShadeIn in{};
+            if (move) in = shade_in<true, 0, false>(pa, item, geo_in, tz_in, rid_in, hits, nullptr);   // overlaps the ranking
+            const unsigned long long peers = match_bucket(b, valid);
+            const uint32_t rank = rank_below(peers);
+            if (valid && rank == 0) wcount[wave][b] = (uint32_t)__popcll(peers);
+            __syncthreads();
+            if (move) {
+                uint32_t pos = run[b] + rank;
+                for (int k = 0; k < wave; k++) pos += wcount[k][b];
+                in.seed = pos;          // the reference's slot of this ray at bounce 1 (raytracing.cu:89)
+                const Shaded sh = shade_from<true, 0>(S, pa, item, in, seed_term);
+                const V3 no = sh.no, nd = sh.nd, T = sh.T;
+                miss += sh.kind == 0;
+                hit += sh.kind != 0;
+                hit_sphere += sh.kind == 2;
+                const bool dead = is_black(T);
+                const bool term = has_radiance(sh.C);
+                if (dead || last || term) {
+                    V3 C = sh.C;
+                    if (sh.acc_holds) {
+                        const float4 a = acc[sh.ray];
+                        C = v3(a.y, a.z, a.w) + sh.C;
+                    }
+                    typedef float f4v __attribute__((ext_vector_type(4)));
+                    if (dead || last)
+                        __builtin_nontemporal_store(f4v{T.z, C.x, C.y, C.z}, reinterpret_cast<f4v *>(acc + sh.ray));
+                    else
+                        acc[sh.ray] = make_float4(T.z, C.x, C.y, C.z);   // read back at a later bounce
+                }
+                if (!dead && !last) {
+                    geo_out[(size_t)pos * 2] = make_float4(no.x, no.y, no.z, nd.x);
+                    geo_out[(size_t)pos * 2 + 1] = make_float4(nd.y, nd.z, T.x, T.y);
+                    tz_out[pos] = T.z;
+                    rid_out[pos] = sh.ray | (term || sh.acc_holds ? kAccFlag : 0u);
+                    bkt_out[pos] = (uint8_t)bucket_of(no, nd, S.min_coord, S.inv_dim);
+                }
+            }
+            __syncthreads();
+            if (threadIdx.x < kBuckets) {
+                uint32_t s = 0;
+                for (int k = 0; k < kBlock / 64; k++) { s += wcount[k][threadIdx.x]; wcount[k][threadIdx.x] = 0; }
+                run[threadIdx.x] += s;
+            }
+            __syncthreads();
+        }
+    }
+    if (COUNT) {
+        Counters *cs = ctr + ((blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) & (kCtrSlots - 1));
+        const unsigned long long h = wave_sum(hit), m = wave_sum(miss), hs = wave_sum(hit_sphere);
+        if (lane_id() == 0 && (h | m)) {
+            atomicAdd(&cs->hits, h);
+            atomicAdd(&cs->misses, m);
+            atomicAdd(&cs->hits_sphere, hs);
+        }
+    }
+}
+
 // ---------------------------------------------------------------- accumulate
 // Ordered per-pixel sum of the pass's samples (the caller then adds it: fb += sum, in pass order) (raytracing.cu:96-107 without
 // the unordered atomics; the CPU path's order, raytracing.cu:114-120).
@@ -1303,6 +1424,7 @@ struct PassCtx {
     DevBuf<float> tz[2];
     DevBuf<uint32_t> rid[2], sort_counts, sort_offsets, sort_totals, live, queue, overflow;
     DevBuf<uint8_t> bkt;
+    DevBuf<uint8_t> bkt1;             // Renderer::vre: the bounce-1 buckets at the sorted positions (bkt: bounce 0's, by ray id)
     DevBuf<float2> hits;
     // Renderer::home: acc holds 2 x max_rays entries (ray ids below max_rays for rays terminated at bounce 0,
     // home indices from max_rays on for the rest); home_of[ray id] = where the ray's radiance is
@@ -1371,6 +1493,11 @@ struct rt_renderer {
     // bounce-1 slot) instead of acc[ray id] (sort_scatter_shade_kernel).  RTAMD_HOME=0: ray ids throughout.
     bool home = false;
     uint32_t home_base = 0;
+    // Virtual bounce-0 reorder (shade_rank_kernel): sort on, untiled, a scene with triangles, at least 2 bounces, and
+    // a scene big enough that only bounce 0 would use the fused reorder, RTAMD_FUSED unset (set, it names the moved
+    // reorder to run).  RTAMD_VREORDER: 0 never, 1 whatever the scene's size and RTAMD_FUSED.  Radiance stays in
+    // acc[ray id] (no home index).
+    bool vre = false;
     int width = 0, height = 0, spp = 0, bounces = 0;
     SceneDev scene;                   // the device arrays, the DevScene the kernels take, the work counters
     DevBuf<float> fb;
@@ -1487,13 +1614,17 @@ struct rt_renderer {
         trace_blocks_max = std::max(1, scene.cus * std::max(1, per_cu));
         trace_blocks = trace_blocks_max;
         const int tiles = tile_stride(max_rays);
-        home = sort && !tiled() && bounces >= 2 && (fused || fused_upto >= 0);
+        // the default only while RTAMD_FUSED is unset: a set RTAMD_FUSED asks for the moved reorder it names
+        const bool vre_can = sort && !tiled() && bounces >= 2 && sc->triangle_count > 0;
+        vre = vre_can && !std::getenv("RTAMD_FUSED") && !fused && fused_upto == 0;
+        if (const char *e = std::getenv("RTAMD_VREORDER")) vre = vre_can && std::atoi(e) != 0;
+        home = !vre && sort && !tiled() && bounces >= 2 && (fused || fused_upto >= 0);
         if (const char *e = std::getenv("RTAMD_HOME")) home = home && std::atoi(e) != 0;
         home_base = (uint32_t)max_rays;
         // Passes in flight: up to kInflight, as many as the frame has, and no more contexts
         // than half of the free device memory holds (1080p: ~2.9 GB per context).
         const size_t ctx_bytes = (size_t)max_rays * (2 * (32 + 4 + 4) + 16 + 1 + 8 + (tsort() ? 2 * 4 + 4 + 2 : 0) +
-                                                     (home ? 16 + 4 : 0)) +
+                                                     (home ? 16 + 4 : 0) + (vre ? 1 : 0)) +
                                  (size_t)trace_blocks_max * kBlock * 8 * (kStackMax - kStackLds) + ((size_t)1 << 20);
         size_t mem_free = 0, mem_total = 0;
         HIPCHK(hipMemGetInfo(&mem_free, &mem_total));
@@ -1523,6 +1654,7 @@ struct rt_renderer {
                 if ((rc = c.rid[q].alloc((size_t)max_rays))) return rc;
             }
             if ((rc = c.bkt.alloc((size_t)max_rays))) return rc;
+            if (vre && (rc = c.bkt1.alloc((size_t)max_rays))) return rc;
             if ((rc = c.acc.alloc((size_t)max_rays * (home ? 2 : 1)))) return rc;
             if (home && (rc = c.home_of.alloc((size_t)max_rays))) return rc;
             if ((rc = c.sort_counts.alloc((size_t)kBuckets * tiles))) return rc;
@@ -1548,6 +1680,7 @@ struct rt_renderer {
         HIPCHK(hipMemsetAsync(fb.p, 0, fb.n * sizeof(float), s0));
         HIPCHK(hipStreamSynchronize(s0));
         tm.mark("sync");
+        if (tm.on) tm.out += vre ? " bounce-0 reorder: virtual" : " bounce-0 reorder: moved";
         tm.report();
         return RT_OK;
     }
@@ -1599,8 +1732,12 @@ struct rt_renderer {
             const uint32_t *lv = c.live.p + b;
             uint32_t *q = c.queue.p + (size_t)b * kQueues * kQueueStride;
             const bool last = b + 1 == bounces;
-            uint32_t *hist = shade_hist && !last ? c.sort_counts.p : nullptr;   // the shade kernel counts the buckets
-#define RT_PROCESS3(SORTED, COUNT, FIRST)                                                                         \
+            // virtual reorder: bounce 0 shades in place (not fused), bounce 1 runs over the ray-id slots
+            const bool v0 = vre && b == 0, v1 = vre && b == 1;
+            const bool fuse_b = !v0 && !v1 && (fused || b <= fused_upto);
+            // the shade kernel counts the buckets (bounce 1 of the virtual reorder: sort_hist_kernel, over the sorted positions)
+            uint32_t *hist = shade_hist && !last && !v1 ? c.sort_counts.p : nullptr;
+#define RT_PROCESS3(SORTED, COUNT, FIRST)                                                                        \
     do {                                                                                                         \
         if (!inline_hits)                                                                                        \
             hipLaunchKernelGGL((trace_kernel<SORTED, COUNT, FIRST>), dim3(tgrid), dim3(kBlock), 0, st, scene.ds, pa, \
@@ -1611,7 +1748,7 @@ struct rt_renderer {
             hipLaunchKernelGGL((shade_kernel<SORTED, COUNT, FIRST, true, true>), dim3(sgrid), dim3(kBlock), 0, st,\
                                scene.ds, pa, c.geo[cur].p, c.tz[cur].p, c.rid[cur].p, c.acc.p, c.bkt.p, lv, c.hits.p, \
                                seed_term, (int)last, scene.ctr.p, nullptr, hist, tiles, (int)(home && b == 0));  \
-        else if (fused || b <= fused_upto)                                                                       \
+        else if (fuse_b)                                                                                         \
             hipLaunchKernelGGL((shade_kernel<SORTED, COUNT, FIRST, true, false>), dim3(sgrid), dim3(kBlock), 0, \
                                st, scene.ds, pa, c.geo[cur].p, c.tz[cur].p, c.rid[cur].p, c.acc.p, c.bkt.p, lv, c.hits.p, \
                                seed_term, (int)last, scene.ctr.p, nullptr, hist, tiles, (int)(home && b == 0));  \
@@ -1624,7 +1761,24 @@ struct rt_renderer {
     do {                                                                                                         \
         if (b == 0) RT_PROCESS3(SORTED, COUNT, 1); else RT_PROCESS3(SORTED, COUNT, 0);                           \
     } while (0)
-            if (sort) {
+            if (v1) {
+                // every slot of the pass (live[0]); the state is still in ray-id order, the survivors' new state
+                // goes to their sorted positions of the other buffer set
+#define RT_VPROCESS(COUNT)                                                                                       \
+    do {                                                                                                         \
+        hipLaunchKernelGGL((trace_kernel<true, COUNT, 0, true>), dim3(tgrid), dim3(kBlock), 0, st, scene.ds, pa, \
+                           c.geo[cur].p, c.live.p, q, c.hits.p, c.overflow.p, scene.ctr.p,                       \
+                           tspan ? tspan + kSpanWords * b : nullptr, c.bkt.p);                                   \
+        if (em) HIPCHK(hipEventRecord(em, st));                                                                  \
+        hipLaunchKernelGGL((shade_rank_kernel<COUNT>), dim3(sort_grid), dim3(kBlock), 0, st, scene.ds, pa, c.bkt.p, \
+                           c.geo[cur].p, c.tz[cur].p, c.rid[cur].p, c.hits.p, seed_term, (int)last, c.live.p, tiles, \
+                           c.sort_offsets.p, c.sort_totals.p, c.geo[1 - cur].p, c.tz[1 - cur].p, c.rid[1 - cur].p, \
+                           c.bkt1.p, c.acc.p, scene.ctr.p);                                                      \
+    } while (0)
+                if (counters) RT_VPROCESS(true); else RT_VPROCESS(false);
+#undef RT_VPROCESS
+                cur = 1 - cur;
+            } else if (sort) {
                 if (counters) RT_PROCESS(true, true); else RT_PROCESS(true, false);
             } else {
                 if (b == 0 && tiled()) {        // pixel tile (sort off only): mapped bounce-0 slots
@@ -1644,12 +1798,18 @@ struct rt_renderer {
                     if (!s0 || !s1) return rtamd::fail(RT_E_HIP, "hipEventCreate failed");
                     HIPCHK(hipEventRecord(s0, st));
                 }
+                const uint8_t *bk = v1 ? c.bkt1.p : c.bkt.p;
                 if (!hist)
-                    hipLaunchKernelGGL(sort_hist_kernel, dim3(sort_grid), dim3(kBlock), 0, st, c.bkt.p, lv, tiles,
+                    hipLaunchKernelGGL(sort_hist_kernel, dim3(sort_grid), dim3(kBlock), 0, st, bk, lv, tiles,
                                        c.sort_counts.p);
                 hipLaunchKernelGGL(sort_scan_kernel, dim3(kBuckets), dim3(kBlock), 0, st, c.sort_counts.p, lv, tiles,
                                    c.sort_offsets.p, c.sort_totals.p, c.live.p + b + 1);
-                if (fused || b <= fused_upto) {
+                if (v0) {
+                    // nothing moves: the runs and the bounce-1 live count are all bounce 1 needs (shade_rank_kernel);
+                    // its buckets start as holes
+                    if (b + 2 != bounces)
+                        hipLaunchKernelGGL(fill_dead_kernel, dim3(sort_grid), dim3(kBlock), 0, st, c.bkt1.p, c.live.p + 1);
+                } else if (fuse_b) {
 #define RT_FSC2(SO, FI, IN)                                                                                      \
     hipLaunchKernelGGL((sort_scatter_shade_kernel<SO, FI, IN>), dim3(sort_grid), dim3(kBlock), 0, st, scene.ds, pa, \
                        c.bkt.p, c.geo[cur].p, c.tz[cur].p, c.rid[cur].p, c.hits.p, seed_term, lv, tiles,          \
@@ -1672,12 +1832,12 @@ struct rt_renderer {
                                        c.tz[cur].p, c.rid[cur].p, lv, tiles, c.sort_offsets.p, c.sort_totals.p,
                                        c.geo[1 - cur].p, c.tz[1 - cur].p, c.rid[1 - cur].p, pa.map);
                 else
-                    hipLaunchKernelGGL(sort_scatter_kernel<0>, dim3(sort_grid), dim3(kBlock), 0, st, c.bkt.p, c.geo[cur].p,
+                    hipLaunchKernelGGL(sort_scatter_kernel<0>, dim3(sort_grid), dim3(kBlock), 0, st, bk, c.geo[cur].p,
                                        c.tz[cur].p, c.rid[cur].p, lv, tiles, c.sort_offsets.p, c.sort_totals.p,
                                        c.geo[1 - cur].p, c.tz[1 - cur].p, c.rid[1 - cur].p, pa.map);
                 HIPCHK(hipGetLastError());
                 if (pass_events) HIPCHK(hipEventRecord(s1, st));
-                cur = 1 - cur;
+                if (!v0) cur = 1 - cur;
                 if (sort) sorted += n;
             }
         }
