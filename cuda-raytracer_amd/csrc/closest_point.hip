@@ -307,11 +307,16 @@ int closest_point_blocks_per_cu(int &per_cu) {
     return RT_OK;
 }
 
+void launch_point_ingest(int n, hipStream_t s, const float *d_points, const float *d_max_dist, float4 *geo, uint32_t *live,
+                         uint32_t *queue, Counters *ctr) {
+    hipLaunchKernelGGL(point_ingest_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, s, d_points, d_max_dist, (uint32_t)n, geo,
+                       live, queue, ctr);
+}
+
 void launch_closest_point(bool count, int n, int grid, hipStream_t s, const DevScene &ds, const float *d_points,
                           const float *d_max_dist, float4 *geo, uint32_t *live, uint32_t *queue,
                           const rt_closest_point_out &out, uint32_t *overflow, Counters *ctr) {
-    hipLaunchKernelGGL(point_ingest_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, s, d_points, d_max_dist, (uint32_t)n, geo,
-                       live, queue, ctr);
+    launch_point_ingest(n, s, d_points, d_max_dist, geo, live, queue, ctr);
     if (count)
         hipLaunchKernelGGL(closest_point_kernel<true>, dim3(grid), dim3(kBlock), 0, s, ds, geo, live, queue, out, overflow, ctr);
     else

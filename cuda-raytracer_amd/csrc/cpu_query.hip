@@ -8,6 +8,8 @@
 //
 // Also rt_scene_closest_point, the host twin of rt_query_closest_point: the pinned walk with the
 // shrinking bound, every value from closest_point_math.h, which the device kernel compiles too.
+// And rt_scene_nearest_k, the host twin of rt_query_nearest_k: the same arithmetic with the bound held,
+// every member of the fixed set collected and sorted by the key (dist2 bits, index).
 #include "rt_abi.h"
 #include "rt_device.h"
 #include "closest_point_math.h"
@@ -117,7 +119,86 @@ void nearest(const rt_scene &s, rt_vec3 p, float &best2, int32_t &best, std::vec
     }
 }
 
+// rt_scene_nearest_k's set H (rt_abi.h) for one finite point: nearest_k_kernel's walk with the bound b2
+// held, over the scene's own node array.  The stack holds nodes only -- every pushed child has passed the test it
+// would meet at the pop -- and the set does not depend on the order.
+struct Member { uint32_t key; int32_t index; float dist2; };
+
+void members(const rt_scene &s, rt_vec3 p, float b2, std::vector<Member> &found, std::vector<int32_t> &stack) {
+    namespace cp = rtamd::cp;
+    found.clear();
+    for (int i = 0; i < s.sphere_count; i++) {
+        rt_vec3 w;
+        float len;
+        const float d2 = cp::sphere_dist2(p, s.spheres[i].center, s.spheres[i].radius, w, len);
+        if (cp::within(d2, b2)) found.push_back({cp::key_bits(d2), i, d2});
+    }
+    if (0.0f > b2) return;
+    stack.clear();
+    stack.push_back(0);
+    while (!stack.empty()) {
+        const rt_bvh_node &nd = s.bvh[stack.back()];
+        stack.pop_back();
+        if (nd.child2 <= nd.child1) {
+            for (int j = nd.child2; j < nd.child1; j++) {
+                const rt_triangle &tr = s.triangles[j];
+                const float d2 = cp::triangle(p, tr.p1, tr.p2p1, tr.p3p1).dist2;
+                if (cp::within(d2, b2)) found.push_back({cp::key_bits(d2), s.sphere_count + j, d2});
+            }
+            continue;
+        }
+        const rt_bvh_node &c1 = s.bvh[nd.child1], &c2 = s.bvh[nd.child2];
+        const float a = cp::box2(p, c1.min_bound, c1.max_bound), b = cp::box2(p, c2.min_bound, c2.max_bound);
+        const bool e1 = !(a > b2), e2 = !(b > b2);
+        const bool second = e2 && (!e1 || b < a);      // the nearer child first, a tie to child1: the kernel's order
+        if (e1 && e2) stack.push_back(second ? nd.child1 : nd.child2);
+        if (e1 || e2) stack.push_back(second ? nd.child2 : nd.child1);
+    }
+}
+
 }  // namespace
+
+extern "C" int rt_scene_nearest_k(const rt_scene *s, const float *points, const float *max_dist, int32_t n, int32_t k,
+                                  const rt_nearest_k_out *out) {
+    namespace cp = rtamd::cp;
+    if (!s) return rtamd::fail(RT_E_INVALID, "rt_scene_nearest_k: null scene");
+    if (n < 0) return rtamd::fail(RT_E_INVALID, "rt_scene_nearest_k: negative point count");
+    if (k < 1 || k > RT_NEAREST_K_MAX)
+        return rtamd::fail(RT_E_INVALID, "rt_scene_nearest_k: k " + std::to_string(k) + " is outside 1.." +
+                                             std::to_string(RT_NEAREST_K_MAX));
+    if (n == 0) return RT_OK;
+    if (!points || !out) return rtamd::fail(RT_E_INVALID, "rt_scene_nearest_k: null pointer");
+    if ((int64_t)n * k > INT32_MAX)
+        return rtamd::fail(RT_E_INVALID, "rt_scene_nearest_k: n * k = " + std::to_string((int64_t)n * k) + " does not fit int32");
+    if (s->bvh_node_count < 1 || !s->bvh) return rtamd::fail(RT_E_INVALID, "rt_scene_nearest_k: scene has no BVH root");
+    std::vector<Member> found;
+    std::vector<int32_t> stack;
+    for (int32_t i = 0; i < n; i++) {
+        const rt_vec3 p = {points[(size_t)i * 3], points[(size_t)i * 3 + 1], points[(size_t)i * 3 + 2]};
+        const float b2 = max_dist ? cp::bound2(max_dist[i]) : INFINITY;
+        found.clear();
+        if (cp::finite3(p)) members(*s, p, b2, found, stack);
+        std::sort(found.begin(), found.end(),
+                  [](const Member &a, const Member &b) { return cp::key_less(a.key, a.index, b.key, b.index); });
+        if (out->count) out->count[i] = (int32_t)found.size();
+        for (int32_t j = 0; j < k; j++) {
+            const size_t e = (size_t)i * k + j;
+            const bool have = (size_t)j < found.size();
+            if (out->distance) out->distance[e] = have ? sqrtf(found[j].dist2) : 1e30f;
+            if (out->index) out->index[e] = have ? found[j].index : -1;
+            if (!out->point) continue;
+            rt_vec3 q{0.0f, 0.0f, 0.0f};
+            if (have && found[j].index < s->sphere_count) {
+                q = cp::sphere(p, s->spheres[found[j].index].center, s->spheres[found[j].index].radius).point;
+            } else if (have) {
+                const rt_triangle &tr = s->triangles[found[j].index - s->sphere_count];
+                q = cp::triangle(p, tr.p1, tr.p2p1, tr.p3p1).point;
+            }
+            out->point[e * 3] = q.x; out->point[e * 3 + 1] = q.y; out->point[e * 3 + 2] = q.z;
+        }
+    }
+    return RT_OK;
+}
 
 extern "C" int rt_scene_closest_point(const rt_scene *s, const float *points, const float *max_dist, int32_t n,
                                       const rt_closest_point_out *out) {

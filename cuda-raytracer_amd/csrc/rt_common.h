@@ -220,5 +220,17 @@ int closest_point_blocks_per_cu(int &per_cu);
 void launch_closest_point(bool count, int n, int grid, hipStream_t s, const DevScene &ds, const float *d_points,
                           const float *d_max_dist, float4 *geo, uint32_t *live, uint32_t *queue,
                           const rt_closest_point_out &out, uint32_t *overflow, Counters *ctr);
+// point_ingest_kernel alone (closest_point.hip), for the other point query
+void launch_point_ingest(int n, hipStream_t s, const float *d_points, const float *d_max_dist, float4 *geo, uint32_t *live,
+                         uint32_t *queue, Counters *ctr);
+
+// nearest_k_kernel (nearest_k.hip) for rt_query.hip: the traversal with the bound held, over points
+// already ingested into `geo`.  ld / li: each point's k list rows (dist2 while it runs, the distance afterwards, and
+// the index), both null = count only; point (n x k x 3) and count (n) are optional.
+constexpr int kAnyStackLds = 16;      // 4-B stack entries per lane in LDS of the fixed-bound kernels
+int nearest_k_blocks_per_cu(int &per_cu);
+void launch_nearest_k(bool count, int grid, hipStream_t s, const DevScene &ds, const float4 *geo, const uint32_t *live,
+                      uint32_t *queue, int k, float *ld, int32_t *li, float *point, int32_t *count_out, uint32_t *overflow,
+                      Counters *ctr);
 
 }  // namespace rtamd

@@ -2,7 +2,8 @@
 // them: the ingest, egest, hit-record, any-hit and multi-hit kernels, the query object
 // and its C ABI.
 // The closest-hit traversal is the renderer's trace_kernel, compiled in rt_render.hip and launched through
-// rt_common.h, as is the closest-point traversal of closest_point.hip; the refit of rt_query_update_triangles is bvh_refit.hip.
+// rt_common.h, as are the closest-point traversal of closest_point.hip and the nearest-k one of
+// nearest_k.hip; the refit of rt_query_update_triangles is bvh_refit.hip.
 #include "rt_common.h"
 #include "bvh_refit.h"
 #include "bvh_refit_math.h"
@@ -140,7 +141,7 @@ __global__ __launch_bounds__(kBlock) void query_hit_egest_kernel(const float2 *_
 // the other one is pushed iff both are entered; a leaf's triangles in order; an exhausted leaf, or a node
 // with no entered child, pops.  tests/anyhit_ref.py (AnyHitOrderRef) restates it and
 // tests/test_gpu_anyhit_order.py pins the counters to it on all rays, occluded ones included.
-constexpr int kAnyStackLds = 16;
+// (kAnyStackLds is rt_common.h's: nearest_k.hip uses the same stack.)
 
 template <bool COUNT>
 __global__ __launch_bounds__(kBlock) RT_TRACE_ATTR void anyhit_kernel(DevScene S, const float4 *__restrict__ geo,
@@ -653,9 +654,12 @@ struct rt_query {
     size_t list_cap = 0, host_list_cap = 0;
     DevBuf<float> list_t, s_list_t;
     DevBuf<int32_t> list_i, s_list_i, s_count;
+    // nearest_k shares those; nearest_k_host's staging of point (n*k*3)
+    size_t host_point_cap = 0;
+    DevBuf<float> s_list_p;
     hipEvent_t last = nullptr;
     bool pending = false;             // `last` has been recorded
-    int last_kind = 0;                // 0 none (or an update), 1 closest, 2 occluded, 3 multi_hit, 4 closest_point
+    int last_kind = 0;                // 0 none (or an update), 1 closest, 2 occluded, 3 multi_hit, 4 closest_point, 5 nearest_k
     int32_t last_n = 0;
     rtamd::RefitPlan plan;            // rt_query_update_triangles: level tables, built in init
 
@@ -678,16 +682,18 @@ struct rt_query {
         HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         int rc = scene.init(sc, o->device, stream);
         if (rc) return rc;
-        int per_cu_c = 0, per_cu_a = 0, per_cu_m = 0, per_cu_p = 0;
-        if ((rc = trace_closest_blocks_per_cu(per_cu_c)) || (rc = closest_point_blocks_per_cu(per_cu_p))) return rc;
+        int per_cu_c = 0, per_cu_a = 0, per_cu_m = 0, per_cu_p = 0, per_cu_n = 0;
+        if ((rc = trace_closest_blocks_per_cu(per_cu_c)) || (rc = closest_point_blocks_per_cu(per_cu_p)) ||
+            (rc = nearest_k_blocks_per_cu(per_cu_n)))
+            return rc;
         HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_a, anyhit_kernel<false>, kBlock, 0));
         HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_m, multihit_kernel<false>, kBlock, 0));
-        blocks = std::max(1, scene.cus * std::max({1, per_cu_c, per_cu_a, per_cu_m, per_cu_p}));
+        blocks = std::max(1, scene.cus * std::max({1, per_cu_c, per_cu_a, per_cu_m, per_cu_p, per_cu_n}));
         HIPCHK(hipEventCreateWithFlags(&last, hipEventDisableTiming));
         if ((rc = words.alloc((size_t)(1 + kQueues) * kQueueStride))) return rc;
         if ((rc = plan.build(sc, scene.node_rec, stream))) return rc;
         // trace_kernel: 2 words (ref, distance) for each of kStackMax - kStackLds entries per lane; the
-        // any-hit and multi-hit kernels' kStackMax - kAnyStackLds one-word entries fit in the same buffer
+        // any-hit, multi-hit and nearest-k kernels' kStackMax - kAnyStackLds one-word entries fit in the same buffer
         return overflow.alloc((size_t)blocks * kBlock * 2 * (kStackMax - kStackLds));
     }
     int wait_last() {
@@ -838,6 +844,71 @@ struct rt_query {
         if (out.index) HIPCHK(hipMemcpyAsync(out.index, d.index, m * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         if (out.uv) HIPCHK(hipMemcpyAsync(out.uv, d.uv, m * 2 * sizeof(float), hipMemcpyDeviceToHost, s));
         if (out.point) HIPCHK(hipMemcpyAsync(out.point, d.point, m * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return RT_OK;
+    }
+    // Every primitive within max_dist, the k nearest kept.  The kernel keeps each point's list
+    // (dist2, index) in the caller's distance and index rows; a half the caller left out lives in the multi-hit list
+    // scratch when any of distance, index and point is asked for, and with none of them the kernel only counts.
+    int nearest_k(const float *d_points, const float *d_max_dist, int n, int k, const rt_nearest_k_out &out, hipStream_t s) {
+        float *ld = out.distance;
+        int32_t *li = out.index;
+        const bool keep = ld || li || out.point;
+        if (keep && (!ld || !li)) {
+            const size_t need = (size_t)n * k;
+            if (need > list_cap) {
+                HIPCHK(hipSetDevice(scene.device));
+                int rc = wait_last();       // the last call may still use the old lists
+                if (rc) return rc;
+                const size_t want = std::max(need, 2 * list_cap);
+                list_cap = 0;
+                if ((rc = list_t.alloc(want)) || (rc = list_i.alloc(want))) return rc;
+                list_cap = want;
+            }
+            if (!ld) ld = list_t.p;
+            if (!li) li = list_i.p;
+        }
+        HIPCHK(hipSetDevice(scene.device));
+        int rc = reserve(n);
+        if (rc) return rc;
+        if (pending) HIPCHK(hipStreamWaitEvent(s, last, 0));
+        launch_point_ingest(n, s, d_points, d_max_dist, geo.p, live(), queue(), scene.ctr.p);
+        launch_nearest_k(counters, std::min(blocks_for(n), blocks), s, scene.ds, geo.p, live(), queue(), k, ld, li, out.point,
+                         out.count, overflow.p, scene.ctr.p);
+        return end(5, n, s);
+    }
+    int nearest_k_host(const float *points, const float *max_dist, int n, int k, const rt_nearest_k_out &out) {
+        int rc = reserve_host(n);
+        if (rc) return rc;
+        const size_t m = (size_t)n * k;
+        if (m > host_list_cap) {
+            HIPCHK(hipSetDevice(scene.device));
+            const size_t want = std::max(m, 2 * host_list_cap);
+            host_list_cap = 0;              // the host calls are blocking: nothing reads the old staging
+            if ((rc = s_list_t.alloc(want)) || (rc = s_list_i.alloc(want))) return rc;
+            host_list_cap = want;
+        }
+        if (out.point && m > host_point_cap) {
+            HIPCHK(hipSetDevice(scene.device));
+            const size_t want = std::max(m, 2 * host_point_cap);
+            host_point_cap = 0;
+            if ((rc = s_list_p.alloc(want * 3))) return rc;
+            host_point_cap = want;
+        }
+        if (s_count.n < host_cap && (rc = s_count.alloc(host_cap))) return rc;
+        hipStream_t s = stream;
+        rt_nearest_k_out d{};
+        if (out.distance) d.distance = s_list_t.p;
+        if (out.index) d.index = s_list_i.p;
+        if (out.point) d.point = s_list_p.p;
+        if (out.count) d.count = s_count.p;
+        HIPCHK(hipMemcpyAsync(s_rays.p, points, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, s));
+        if (max_dist) HIPCHK(hipMemcpyAsync(s_tmax.p, max_dist, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s));
+        if ((rc = nearest_k(s_rays.p, max_dist ? s_tmax.p : nullptr, n, k, d, s))) return rc;
+        if (out.distance) HIPCHK(hipMemcpyAsync(out.distance, d.distance, m * sizeof(float), hipMemcpyDeviceToHost, s));
+        if (out.index) HIPCHK(hipMemcpyAsync(out.index, d.index, m * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        if (out.point) HIPCHK(hipMemcpyAsync(out.point, d.point, m * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
+        if (out.count) HIPCHK(hipMemcpyAsync(out.count, d.count, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         return RT_OK;
     }
@@ -1102,6 +1173,34 @@ int rt_query_closest_point_host(rt_query *q, const float *points, const float *m
     const int rc = closest_point_args("rt_query_closest_point_host", q, points, n, out);
     if (rc) return rc > 0 ? RT_OK : rc;
     return q->closest_point_host(points, max_dist, n, *out);
+}
+
+// The checks shared by the two nearest-k calls; > 0: n == 0, nothing to do.
+static int nearest_k_args(const char *fn, const rt_query *q, const void *points, int32_t n, int32_t k, const void *out) {
+    const std::string f(fn);
+    if (!q) return rtamd::fail(RT_E_INVALID, f + ": null query object");
+    if (n < 0) return rtamd::fail(RT_E_INVALID, f + ": negative point count");
+    if (k < 1 || k > RT_NEAREST_K_MAX)
+        return rtamd::fail(RT_E_INVALID, f + ": k " + std::to_string(k) + " is outside 1.." + std::to_string(RT_NEAREST_K_MAX));
+    if (n == 0) return 1;
+    if (!points || !out) return rtamd::fail(RT_E_INVALID, f + ": null pointer");
+    if ((int64_t)n * k > INT32_MAX)
+        return rtamd::fail(RT_E_INVALID, f + ": n * k = " + std::to_string((int64_t)n * k) + " does not fit int32");
+    return RT_OK;
+}
+
+int rt_query_nearest_k(rt_query *q, const float *d_points, const float *d_max_dist, int32_t n, int32_t k,
+                       const rt_nearest_k_out *d_out, void *hip_stream) {
+    const int rc = nearest_k_args("rt_query_nearest_k", q, d_points, n, k, d_out);
+    if (rc) return rc > 0 ? RT_OK : rc;
+    return q->nearest_k(d_points, d_max_dist, n, k, *d_out, static_cast<hipStream_t>(hip_stream));
+}
+
+int rt_query_nearest_k_host(rt_query *q, const float *points, const float *max_dist, int32_t n, int32_t k,
+                            const rt_nearest_k_out *out) {
+    const int rc = nearest_k_args("rt_query_nearest_k_host", q, points, n, k, out);
+    if (rc) return rc > 0 ? RT_OK : rc;
+    return q->nearest_k_host(points, max_dist, n, k, *out);
 }
 
 int rt_query_stats(rt_query *q, rt_stats *stats) {

@@ -44,6 +44,19 @@ RT_CP_HD bool accepts(float dist2, int32_t i, float best2, int32_t best) {
     return dist2 < best2 || (dist2 == best2 && i < best);
 }
 
+// Range queries (rt_query_nearest_k): the bound b2 is held, a primitive at dist2 is a member iff this
+// holds (a NaN dist2 never is), and so is a node whose box2 passes `!(box2 > b2)`.
+RT_CP_HD bool within(float dist2, float b2) { return dist2 <= b2; }
+
+// Their order: the key (dist2's bits as uint32, index), ascending.  A member's dist2 is a sum of squares, >= +0 and
+// not NaN, so unsigned order is numeric order.
+RT_CP_HD uint32_t key_bits(float dist2) {
+    uint32_t u;
+    __builtin_memcpy(&u, &dist2, sizeof(u));
+    return u;
+}
+RT_CP_HD bool key_less(uint32_t ka, int32_t ia, uint32_t kb, int32_t ib) { return ka < kb || (ka == kb && ia < ib); }
+
 // (u, v) of the point of triangle (p1, e1 = p2 - p1, e2 = p3 - p1) nearest to p
 RT_CP_HD void triangle_uv(rt_vec3 p, rt_vec3 p1, rt_vec3 e1, rt_vec3 e2, float &u, float &v) {
     const rt_vec3 ap = sub(p, p1), bp = sub(ap, e1), cq = sub(ap, e2);

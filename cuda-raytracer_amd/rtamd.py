@@ -137,6 +137,33 @@ def _closest_point_fields(fields):
     return tuple(k for k in CLOSEST_POINT_FIELDS if k in names)
 
 
+class RtNearestKOut(C.Structure):
+    """rt_nearest_k_out: distance (n x k), index (n x k), point (n x k x 3), count (n); every pointer optional."""
+    _fields_ = [(n, P) for n in ("distance", "index", "point", "count")]
+
+
+NEAREST_K_MAX = 64   # RT_NEAREST_K_MAX
+NEAREST_K_FIELDS = tuple(n for n, _ in RtNearestKOut._fields_)
+NEAREST_K_DTYPES = {"distance": np.float32, "index": np.int32, "point": np.float32, "count": np.int32}
+
+
+def _nearest_k_shape(field, n, k):
+    return {"distance": (n, k), "index": (n, k), "point": (n, k, 3), "count": (n,)}[field]
+
+
+def _nearest_k_args(k, fields):
+    """k as an int in 1..NEAREST_K_MAX and the requested fields in NEAREST_K_FIELDS order, or ValueError."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise ValueError("k must be an integer, not %s" % type(k).__name__)
+    if not 1 <= int(k) <= NEAREST_K_MAX:
+        raise ValueError("k must be in 1..%d, not %d" % (NEAREST_K_MAX, int(k)))
+    names = (fields,) if isinstance(fields, str) else tuple(fields)
+    for f in names:
+        if f not in NEAREST_K_DTYPES:
+            raise ValueError("unknown nearest-k field %r (known: %s)" % (f, ", ".join(NEAREST_K_FIELDS)))
+    return int(k), tuple(f for f in NEAREST_K_FIELDS if f in names)
+
+
 def _points_np(points):
     a = np.asarray(points)
     if a.dtype != np.float32:
@@ -376,6 +403,21 @@ class Scene:
         _check(f(self.ptr, _ptr(a), _ptr(md) if md is not None else None, n, C.byref(co)))
         return out
 
+    def nearest_k(self, points, k, max_dist=None, fields=NEAREST_K_FIELDS):
+        """rt_scene_nearest_k: the host twin of RayQuery.nearest_k, no GPU: points (n, 3) float32 and
+        max_dist None or (n,) float32, numpy and contiguous.  Returns a dict of the requested fields, bit for bit what
+        the device call writes."""
+        k, names = _nearest_k_args(k, fields)
+        a = _points_np(points)
+        n = a.shape[0]
+        md = _max_dist_np(max_dist, n)
+        out = {f: np.zeros(_nearest_k_shape(f, n, k), NEAREST_K_DTYPES[f]) for f in names}
+        no = RtNearestKOut(**{f: _ptr(v) for f, v in out.items()})
+        f = lib().rt_scene_nearest_k
+        f.argtypes = [P, P, P, I32, I32, P]
+        _check(f(self.ptr, _ptr(a), _ptr(md) if md is not None else None, n, k, C.byref(no)))
+        return out
+
     def signed_distance(self, points, direction=(0.5773503, 0.5773503, 0.5773503)):
         """The host twin of RayQuery.signed_distance (numpy only): the same composition of closest_point and the
         count-only multi_hit on this host scene, no GPU."""
@@ -568,7 +610,8 @@ class RayQuery:
     closest_hit(rays, fields=...) is closest with the hit record (uv, normal, position, material, front_face),
     and multi_hit(rays, k, tmax=None) -> (t, index, count) the k nearest hits in order with the crossing count,
     under the same rules; closest_point(points, max_dist=None) is the point query (nearest surface point, distance,
-    index, uv) and signed_distance its composition with the crossing parity; update(vertices) moves the triangles under
+    index, uv), nearest_k(points, k, max_dist=None) the range query (every primitive within max_dist, the k nearest in
+    order with their count) and signed_distance closest_point's composition with the crossing parity; update(vertices) moves the triangles under
     the frozen BVH topology."""
 
     def __init__(self, scene, device=0, counters=False, L=None):
@@ -765,6 +808,44 @@ class RayQuery:
         co = RtClosestPointOut(**{k: _ptr(v) for k, v in out.items()})
         f.rt_query_closest_point_host.argtypes = [P, P, P, I32, P]
         _check(f.rt_query_closest_point_host(self.h, _ptr(a), _ptr(md) if md is not None else None, n, C.byref(co)), f)
+        return out
+
+    def nearest_k(self, points, k, max_dist=None, fields=NEAREST_K_FIELDS):
+        """rt_query_nearest_k: for each point every primitive within max_dist (per point, inclusive; None = unbounded)
+        on the resident geometry, the k nearest kept in order.  Returns a dict of the requested fields:
+        distance (n, k) float32, index (n, k) int32, point (n, k, 3) float32 and count (n,) int32 -- count is the number
+        of primitives within max_dist, not capped by k; row entries past min(count, k) are (1e30, -1, zeros).
+        1 <= k <= 64.  Fields that are not requested are neither written nor allocated; fields=() only traverses and
+        counts.  points and max_dist as for closest_point: tensors in, tensors out on
+        torch.cuda.current_stream(device) without any synchronisation; a numpy array takes the _host path (blocking)
+        and gives numpy.  Anything else raises ValueError."""
+        k, names = _nearest_k_args(k, fields)
+        f = self.L
+        if _is_tensor(points):
+            import torch
+            n = self.check_tensor(points, self.device, "points", shape_tail=(3,))
+            if max_dist is not None:
+                if not _is_tensor(max_dist):
+                    raise ValueError("max_dist must be a torch.Tensor when points is one")
+                if self.check_tensor(max_dist, self.device, "max_dist", ()) != n:
+                    raise ValueError("max_dist must have one entry per point")
+            dt = {np.float32: torch.float32, np.int32: torch.int32}
+            out = {x: torch.empty(_nearest_k_shape(x, n, k), dtype=dt[NEAREST_K_DTYPES[x]], device=points.device)
+                   for x in names}
+            no = RtNearestKOut(**{x: v.data_ptr() for x, v in out.items()})
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            f.rt_query_nearest_k.argtypes = [P, P, P, I32, I32, P, P]
+            _check(f.rt_query_nearest_k(self.h, P(points.data_ptr()),
+                                        P(max_dist.data_ptr()) if max_dist is not None else None, n, k, C.byref(no),
+                                        P(stream) if stream else None), f)
+            return out
+        a = _points_np(points)
+        n = a.shape[0]
+        md = _max_dist_np(max_dist, n)
+        out = {x: np.zeros(_nearest_k_shape(x, n, k), NEAREST_K_DTYPES[x]) for x in names}
+        no = RtNearestKOut(**{x: _ptr(v) for x, v in out.items()})
+        f.rt_query_nearest_k_host.argtypes = [P, P, P, I32, I32, P]
+        _check(f.rt_query_nearest_k_host(self.h, _ptr(a), _ptr(md) if md is not None else None, n, k, C.byref(no)), f)
         return out
 
     def signed_distance(self, points, direction=(0.5773503, 0.5773503, 0.5773503)):

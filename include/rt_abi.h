@@ -540,6 +540,69 @@ int rt_query_closest_point_host(rt_query *q, const float *points, const float *m
 int rt_scene_closest_point(const rt_scene *scene, const float *points, const float *max_dist, int32_t n,
                            const rt_closest_point_out *out);
 
+/* Range queries: for a point, every primitive within max_dist -- the K nearest in order, and their count.
+ * The presence of these symbols is the feature probe; RT_ABI_VERSION and every existing struct are unchanged.  No
+ * reference counterpart.  This is to rt_query_closest_point what rt_query_multi_hit is to rt_query_closest.
+ * All arithmetic is the closest-point block's above (bound, triangle, sphere, box: host/closest_point_math.h is the only
+ * statement of it).  points, max_dist and S as there.
+ *   bound        B2 of max_dist[i] by the closest-point rule: R*R for 0 <= R <= 1e18, -1 for R < 0, +inf otherwise
+ *                (larger, +inf, NaN, or a NULL max_dist).  A point with a non-finite component has count = 0 and
+ *                nothing is tested.
+ * H is the set of primitives found with the bound HELD at B2:
+ *   spheres      every sphere j is tested (sphere dist2); it is a member, with index j, iff dist2 <= B2.
+ *   root         entered iff !(0 > B2).
+ *   leaf         in an entered leaf every triangle j of [child2, child1) is tested (triangle dist2); it is a member,
+ *                with index S + j, iff dist2 <= B2.  A NaN dist2 never qualifies.
+ *   internal     a child is entered iff !(box2(child) > B2).
+ *   no exit      nothing stops early and the bound never shrinks.
+ * Every predicate depends on (point, B2, primitive or node) alone, so H is a fixed set whatever order the nodes are
+ * visited in -- the argument made for rt_query_occluded and rt_query_multi_hit.  It does not hold for
+ * rt_query_closest_point: there the bound is the best distance so far, which nodes are entered depends on what was
+ * accepted before, and the visit order is part of that call's definition.
+ * Order: members are sorted by the key (dist2's bit pattern as uint32, index) ascending.  A member's dist2 is a sum of
+ * squares, >= +0 and not NaN, so unsigned order is numeric order; equal dist2 goes to the smaller index.
+ * Outputs, for a caller-chosen k with 1 <= k <= RT_NEAREST_K_MAX (every pointer optional, NULL = not written; with all
+ * NULL the call only traverses and counts):
+ *   count[i]                 |H| as int32, not capped by k;
+ *   entry j < min(|H|, k)    of row i (distance[i*k + j], index[i*k + j], point[(i*k + j)*3..]): the j-th member by the
+ *                            key: sqrtf(dist2), its index, and its nearest point, evaluated once more by the triangle
+ *                            or sphere rule as rt_query_closest_point does;
+ *   entry j >= min(|H|, k)   1e30, -1, (+0, +0, +0).
+ * Exact relations to rt_query_closest_point with the same max_dist:
+ *   1. count >= 1 <=> its index >= 0: before its first accept that walk enters exactly the nodes this one enters.
+ *   2. the key of entry 0 is <= the key of its answer: it tests a subset of what the held bound tests; the two are
+ *      equal wherever its pruning did not slip by rounding.
+ *   3. H is a subset of the brute-force set {dist2 <= B2} over all primitives under the same functions; a primitive of
+ *      that set missing from H has an ancestor node whose float box2 > B2 (box2 and dist2 are rounded independently),
+ *      and that is the only way the two differ.
+ * rt_query_nearest_k follows every rule of rt_query_multi_hit: pointers on q's device, enqueued on hip_stream, joins
+ * the event chain, allocates nothing once the scratch holds n points (rt_query_reserve counts points; when distance or
+ * index is NULL but a list is needed -- any of distance, index, point given -- the missing half's n*k words live in
+ * the object's multi-hit list scratch, which grows the same way) and never waits on the host; d_out is a host struct
+ * of device pointers, read before the call returns; the geometry is the object's current resident geometry
+ * (rt_query_update_triangles).  n == 0 is RT_OK and touches no pointer; a null object (or scene), n < 0, k outside
+ * 1..RT_NEAREST_K_MAX (checked before n == 0, as rt_query_multi_hit does), a null points or out pointer with n > 0, or
+ * an n * k that does not fit int32 is RT_E_INVALID before any HIP call.
+ * rt_query_stats after it: live_segments = n, hits = queries with count >= 1, misses = the rest, hits_sphere = 0; with
+ * collect_counters Pn (nodes entered), Iv, Tt and sphere_tests are the full walk's -- order-independent, exact on every
+ * query.
+ * The _host variant takes host pointers, stages through buffers of the object and blocks.  rt_scene_nearest_k is the
+ * host twin: the same on a host scene (rt_scene.bvh), no GPU, bit for bit the device's output; it refuses the same bad
+ * arguments. */
+#define RT_NEAREST_K_MAX 64
+typedef struct {            /* every pointer optional: NULL = not written */
+    float   *distance;      /* n x k     */
+    int32_t *index;         /* n x k     */
+    float   *point;         /* n x k x 3 */
+    int32_t *count;         /* n         */
+} rt_nearest_k_out;
+int rt_query_nearest_k(rt_query *q, const float *d_points, const float *d_max_dist /* NULL = unbounded */,
+                       int32_t n, int32_t k, const rt_nearest_k_out *d_out, void *hip_stream);
+int rt_query_nearest_k_host(rt_query *q, const float *points, const float *max_dist, int32_t n, int32_t k,
+                            const rt_nearest_k_out *out);
+int rt_scene_nearest_k(const rt_scene *scene, const float *points, const float *max_dist, int32_t n, int32_t k,
+                       const rt_nearest_k_out *out);
+
 /* Replaces the bloom block of main (raytracing.cu:356-393, kernels :21-74): high-pass
  * (luminance > threshold), clamped box blur of `radius` horizontally then vertically,
  * add back.  fb is a host W*H*3 buffer, updated in place. */
