@@ -10,9 +10,13 @@
 // shrinking bound, every value from closest_point_math.h, which the device kernel compiles too.
 // And rt_scene_nearest_k, the host twin of rt_query_nearest_k: the same arithmetic with the bound held,
 // every member of the fixed set collected and sorted by the key (dist2 bits, index).
+// And rt_scene_closest_filtered / rt_scene_occluded_filtered, the host twins of the filtered ray queries:
+// the pinned near-first walk with the shrinking bound and the any-hit walk with the bound held, the filter's
+// arithmetic from ray_filter_math.h.
 #include "rt_abi.h"
 #include "rt_device.h"
 #include "closest_point_math.h"
+#include "ray_filter_math.h"
 
 #include <algorithm>
 #include <cstring>
@@ -156,7 +160,191 @@ void members(const rt_scene &s, rt_vec3 p, float b2, std::vector<Member> &found,
     }
 }
 
+// The filtered ray queries' walks (rt_abi.h) for one ray, over the scene's own node array: the per-ray
+// arithmetic is rt_device.h's and ray_filter_math.h's, which filtered_closest_kernel and filtered_anyhit_kernel
+// compile too.  Work counts the walk's Pn, Iv, Tt and sphere tests.
+struct Filter { float lo, B; int32_t skip; uint32_t rm; const uint32_t *masks; };
+struct Work { uint64_t pn = 0, iv = 0, tt = 0, st = 0; };
+struct FarEntry { int32_t node; float entry; };
+
+Filter filter_of(const rt_ray_filter *f, const uint32_t *masks, int32_t i) {
+    namespace rf = rtamd::rf;
+    Filter r{kEps, 1e30f, -1, rf::kAllBits, masks};
+    if (!f) return r;
+    if (f->tmin) r.lo = rf::lower(f->tmin[i]);
+    if (f->tmax) r.B = rf::upper(f->tmax[i]);
+    if (f->skip) r.skip = f->skip[i];
+    if (f->mask) r.rm = f->mask[i];
+    return r;
+}
+
+bool eligible(const Filter &f, int32_t p) { return rtamd::rf::eligible(p, f.skip, f.masks ? f.masks[p] : rtamd::rf::kAllBits, f.rm); }
+
+bool accept_sphere(const rt_scene &s, const Filter &f, V3 o, V3 d, int k, float bound, float &t) {
+    return rtamd::rf::ray_sphere_lo(o, d, vec(s.spheres[k].center), s.spheres[k].radius, f.lo, bound, t) && eligible(f, k);
+}
+
+bool accept_triangle(const rt_scene &s, const Filter &f, V3 o, V3 d, int j, float bound, float &t) {
+    const rt_triangle &tr = s.triangles[j];
+    return ray_triangle(o, d, vec(tr.p1), vec(tr.p2p1), vec(tr.p3p1), bound, t) && !(t < f.lo) && eligible(f, s.sphere_count + j);
+}
+
+bool child_entered(const rt_scene &s, int32_t c, V3 o, float ix, float iy, float iz, float bound, float &entry) {
+    const rt_bvh_node &b = s.bvh[c];
+    return slab(b.min_bound.x, b.min_bound.y, b.min_bound.z, b.max_bound.x, b.max_bound.y, b.max_bound.z, o, ix, iy, iz,
+                bound, entry) &&
+           !(entry >= bound);
+}
+
+void closest_filtered(const rt_scene &s, const Filter &f, V3 o, V3 d, float &closest, int32_t &index, Work &w,
+                      std::vector<FarEntry> &stack) {
+    closest = f.B;
+    index = -1;
+    for (int k = 0; k < s.sphere_count; k++) {
+        float t;
+        w.st++;
+        if (accept_sphere(s, f, o, d, k, closest, t)) { closest = t; index = k; }
+    }
+    if (0.0f >= closest) return;
+    const float ix = 1 / d.x, iy = 1 / d.y, iz = 1 / d.z;
+    stack.clear();
+    int32_t n = 0;
+    w.pn++;
+    while (true) {
+        const rt_bvh_node &nd = s.bvh[n];
+        bool descend = false;
+        if (nd.child2 <= nd.child1) {
+            for (int j = nd.child2; j < nd.child1; j++) {
+                float t;
+                w.tt++;
+                if (accept_triangle(s, f, o, d, j, closest, t)) { closest = t; index = s.sphere_count + j; }
+            }
+        } else {
+            w.iv++;
+            float t1, t2;
+            const bool e1 = child_entered(s, nd.child1, o, ix, iy, iz, closest, t1);
+            const bool e2 = child_entered(s, nd.child2, o, ix, iy, iz, closest, t2);
+            if (e1 || e2) {
+                const bool second = e2 && (!e1 || t2 < t1);
+                if (e1 && e2) stack.push_back(second ? FarEntry{nd.child1, t1} : FarEntry{nd.child2, t2});
+                n = second ? nd.child2 : nd.child1;
+                w.pn++;
+                descend = true;
+            }
+        }
+        if (descend) continue;
+        bool found = false;
+        while (!stack.empty() && !found) {
+            const FarEntry e = stack.back();
+            stack.pop_back();
+            if (!(e.entry >= closest)) { n = e.node; w.pn++; found = true; }
+        }
+        if (!found) return;
+    }
+}
+
+bool occluded_filtered(const rt_scene &s, const Filter &f, V3 o, V3 d, Work &w, std::vector<int32_t> &stack) {
+    const float B = f.B;
+    for (int k = 0; k < s.sphere_count; k++) {
+        float t;
+        w.st++;
+        if (accept_sphere(s, f, o, d, k, B, t)) return true;
+    }
+    if (0.0f >= B) return false;
+    const float ix = 1 / d.x, iy = 1 / d.y, iz = 1 / d.z;
+    stack.clear();
+    int32_t n = 0;
+    w.pn++;
+    while (true) {
+        const rt_bvh_node &nd = s.bvh[n];
+        bool descend = false;
+        if (nd.child2 <= nd.child1) {
+            for (int j = nd.child2; j < nd.child1; j++) {
+                float t;
+                w.tt++;
+                if (accept_triangle(s, f, o, d, j, B, t)) return true;
+            }
+        } else {
+            w.iv++;
+            float t1, t2;
+            const bool e1 = child_entered(s, nd.child1, o, ix, iy, iz, B, t1);
+            const bool e2 = child_entered(s, nd.child2, o, ix, iy, iz, B, t2);
+            if (e1 || e2) {
+                const bool second = e2 && (!e1 || t2 < t1);
+                if (e1 && e2) stack.push_back(second ? nd.child1 : nd.child2);
+                n = second ? nd.child2 : nd.child1;
+                w.pn++;
+                descend = true;
+            }
+        }
+        if (descend) continue;
+        if (stack.empty()) return false;
+        n = stack.back();
+        stack.pop_back();
+        w.pn++;
+    }
+}
+
+// The checks shared by the two filtered twins; > 0: n == 0, nothing to do.
+int filtered_twin_args(const char *fn, const rt_scene *s, const void *rays, int32_t n) {
+    const std::string f(fn);
+    if (!s) return rtamd::fail(RT_E_INVALID, f + ": null scene");
+    if (n < 0) return rtamd::fail(RT_E_INVALID, f + ": negative ray count");
+    if (n == 0) return 1;
+    if (!rays) return rtamd::fail(RT_E_INVALID, f + ": null pointer");
+    if (s->bvh_node_count < 1 || !s->bvh) return rtamd::fail(RT_E_INVALID, f + ": scene has no BVH root");
+    return RT_OK;
+}
+
+void fill_stats(rt_stats *st, int32_t n, const Work &w, uint64_t hits, uint64_t hits_sphere) {
+    if (!st) return;
+    std::memset(st, 0, sizeof(*st));
+    st->live_segments = (uint64_t)n;
+    st->nodes_popped = w.pn; st->internal_visits = w.iv; st->triangle_tests = w.tt; st->sphere_tests = w.st;
+    st->hits = hits; st->misses = (uint64_t)n - hits; st->hits_sphere = hits_sphere;
+}
+
 }  // namespace
+
+extern "C" int rt_scene_closest_filtered(const rt_scene *s, const uint32_t *masks, const float *rays,
+                                         const rt_ray_filter *filter, int32_t n, float *t_out, int32_t *index_out,
+                                         rt_stats *stats) {
+    const int rc = filtered_twin_args("rt_scene_closest_filtered", s, rays, n);
+    if (rc) return rc > 0 ? RT_OK : rc;
+    std::vector<FarEntry> stack;
+    Work w;
+    uint64_t hits = 0, hits_sphere = 0;
+    for (int32_t i = 0; i < n; i++) {
+        const float *r = rays + (size_t)i * 6;
+        float closest;
+        int32_t index;
+        closest_filtered(*s, filter_of(filter, masks, i), v3(r[0], r[1], r[2]), v3(r[3], r[4], r[5]), closest, index, w, stack);
+        if (t_out) t_out[i] = index < 0 ? 1e30f : closest;
+        if (index_out) index_out[i] = index;
+        hits += index >= 0;
+        hits_sphere += index >= 0 && index < s->sphere_count;
+    }
+    fill_stats(stats, n, w, hits, hits_sphere);
+    return RT_OK;
+}
+
+extern "C" int rt_scene_occluded_filtered(const rt_scene *s, const uint32_t *masks, const float *rays,
+                                          const rt_ray_filter *filter, int32_t n, uint8_t *occluded, rt_stats *stats) {
+    const int rc = filtered_twin_args("rt_scene_occluded_filtered", s, rays, n);
+    if (rc) return rc > 0 ? RT_OK : rc;
+    if (!occluded) return rtamd::fail(RT_E_INVALID, "rt_scene_occluded_filtered: null pointer");
+    std::vector<int32_t> stack;
+    Work w;
+    uint64_t hits = 0;
+    for (int32_t i = 0; i < n; i++) {
+        const float *r = rays + (size_t)i * 6;
+        const bool occ = occluded_filtered(*s, filter_of(filter, masks, i), v3(r[0], r[1], r[2]), v3(r[3], r[4], r[5]), w, stack);
+        occluded[i] = occ ? 1 : 0;
+        hits += occ;
+    }
+    fill_stats(stats, n, w, hits, 0);
+    return RT_OK;
+}
 
 extern "C" int rt_scene_nearest_k(const rt_scene *s, const float *points, const float *max_dist, int32_t n, int32_t k,
                                   const rt_nearest_k_out *out) {

@@ -233,4 +233,18 @@ void launch_nearest_k(bool count, int grid, hipStream_t s, const DevScene &ds, c
                       uint32_t *queue, int k, float *ld, int32_t *li, float *point, int32_t *count_out, uint32_t *overflow,
                       Counters *ctr);
 
+// filtered_closest_kernel and filtered_anyhit_kernel (ray_filter.hip) for rt_query.hip: the ingest of n
+// rays and their filter (a host struct of device pointers, each optional) into `geo` (the ray's lower bound in the
+// slot's spare word) and `fil` ({skip, ray mask} per ray), and the two traversals.  masks: the object's primitive
+// mask words, or null when it holds none.  The closest one writes {t, index} records for the egest kernels.
+int ray_filter_blocks_per_cu(int &per_cu_closest, int &per_cu_anyhit);
+void launch_filter_ingest(int n, hipStream_t s, const float *d_rays, const rt_ray_filter &f, float4 *geo, uint2 *fil,
+                          uint32_t *live, uint32_t *queue, Counters *ctr);
+void launch_filtered_closest(bool count, int grid, hipStream_t s, const DevScene &ds, const float4 *geo, const uint2 *fil,
+                             const uint32_t *masks, const uint32_t *live, uint32_t *queue, float2 *hits, uint32_t *overflow,
+                             Counters *ctr);
+void launch_filtered_anyhit(bool count, int grid, hipStream_t s, const DevScene &ds, const float4 *geo, const uint2 *fil,
+                            const uint32_t *masks, const uint32_t *live, uint32_t *queue, uint8_t *out, uint32_t *overflow,
+                            Counters *ctr);
+
 }  // namespace rtamd

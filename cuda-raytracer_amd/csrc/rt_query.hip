@@ -3,7 +3,8 @@
 // and its C ABI.
 // The closest-hit traversal is the renderer's trace_kernel, compiled in rt_render.hip and launched through
 // rt_common.h, as are the closest-point traversal of closest_point.hip and the nearest-k one of
-// nearest_k.hip; the refit of rt_query_update_triangles is bvh_refit.hip.
+// nearest_k.hip and the filtered ray queries' ingest and traversals of ray_filter.hip; the
+// refit of rt_query_update_triangles is bvh_refit.hip.
 #include "rt_common.h"
 #include "bvh_refit.h"
 #include "bvh_refit_math.h"
@@ -657,9 +658,20 @@ struct rt_query {
     // nearest_k shares those; nearest_k_host's staging of point (n*k*3)
     size_t host_point_cap = 0;
     DevBuf<float> s_list_p;
+    // the filtered ray queries: {skip, ray mask} per ray, grown with geo and hits; the primitive
+    // mask words (S + T, allocated in init, read by the kernels only while has_masks); the host calls' staging
+    DevBuf<uint2> fil;
+    DevBuf<uint32_t> masks;
+    bool has_masks = false;
+    int32_t prim_count = 0;           // S + T
+    size_t host_filter_cap = 0;
+    DevBuf<float> s_tmin;
+    DevBuf<int32_t> s_skip;
+    DevBuf<uint32_t> s_rmask;
     hipEvent_t last = nullptr;
     bool pending = false;             // `last` has been recorded
-    int last_kind = 0;                // 0 none (or an update), 1 closest, 2 occluded, 3 multi_hit, 4 closest_point, 5 nearest_k
+    int last_kind = 0;                // 0 none (an update, set_masks), 1 closest, 2 occluded, 3 multi_hit, 4 closest_point,
+                                      // 5 nearest_k, 6 closest_filtered, 7 occluded_filtered
     int32_t last_n = 0;
     rtamd::RefitPlan plan;            // rt_query_update_triangles: level tables, built in init
 
@@ -682,18 +694,21 @@ struct rt_query {
         HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         int rc = scene.init(sc, o->device, stream);
         if (rc) return rc;
-        int per_cu_c = 0, per_cu_a = 0, per_cu_m = 0, per_cu_p = 0, per_cu_n = 0;
+        int per_cu_c = 0, per_cu_a = 0, per_cu_m = 0, per_cu_p = 0, per_cu_n = 0, per_cu_fc = 0, per_cu_fa = 0;
         if ((rc = trace_closest_blocks_per_cu(per_cu_c)) || (rc = closest_point_blocks_per_cu(per_cu_p)) ||
-            (rc = nearest_k_blocks_per_cu(per_cu_n)))
+            (rc = nearest_k_blocks_per_cu(per_cu_n)) || (rc = ray_filter_blocks_per_cu(per_cu_fc, per_cu_fa)))
             return rc;
         HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_a, anyhit_kernel<false>, kBlock, 0));
         HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_m, multihit_kernel<false>, kBlock, 0));
-        blocks = std::max(1, scene.cus * std::max({1, per_cu_c, per_cu_a, per_cu_m, per_cu_p, per_cu_n}));
+        blocks = std::max(1, scene.cus * std::max({1, per_cu_c, per_cu_a, per_cu_m, per_cu_p, per_cu_n, per_cu_fc, per_cu_fa}));
+        prim_count = sc->sphere_count + sc->triangle_count;
+        if ((rc = masks.alloc((size_t)prim_count))) return rc;
         HIPCHK(hipEventCreateWithFlags(&last, hipEventDisableTiming));
         if ((rc = words.alloc((size_t)(1 + kQueues) * kQueueStride))) return rc;
         if ((rc = plan.build(sc, scene.node_rec, stream))) return rc;
-        // trace_kernel: 2 words (ref, distance) for each of kStackMax - kStackLds entries per lane; the
-        // any-hit, multi-hit and nearest-k kernels' kStackMax - kAnyStackLds one-word entries fit in the same buffer
+        // trace_kernel and filtered_closest_kernel: 2 words (ref, distance) for each of kStackMax - kStackLds entries
+        // per lane; the any-hit, multi-hit, nearest-k and filtered any-hit kernels' kStackMax - kAnyStackLds one-word
+        // entries fit in the same buffer
         return overflow.alloc((size_t)blocks * kBlock * 2 * (kStackMax - kStackLds));
     }
     int wait_last() {
@@ -707,7 +722,7 @@ struct rt_query {
         if (rc) return rc;
         const size_t want = std::max<size_t>({(size_t)n, 2 * cap, (size_t)kBlock});
         cap = 0;
-        if ((rc = geo.alloc(want * 2)) || (rc = hits.alloc(want))) return rc;
+        if ((rc = geo.alloc(want * 2)) || (rc = hits.alloc(want)) || (rc = fil.alloc(want))) return rc;
         cap = want;
         return RT_OK;
     }
@@ -909,6 +924,114 @@ struct rt_query {
         if (out.index) HIPCHK(hipMemcpyAsync(out.index, d.index, m * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         if (out.point) HIPCHK(hipMemcpyAsync(out.point, d.point, m * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
         if (out.count) HIPCHK(hipMemcpyAsync(out.count, d.count, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return RT_OK;
+    }
+    // The filtered ray queries: ray_filter.hip's ingest and traversals in the scratch of the ray queries;
+    // the closest one's {t, index} records go through the egest kernel of closest_hit.
+    int begin_filtered(const float *d_rays, const rt_ray_filter &f, int n, hipStream_t s) {
+        HIPCHK(hipSetDevice(scene.device));
+        int rc = reserve(n);
+        if (rc) return rc;
+        if (pending) HIPCHK(hipStreamWaitEvent(s, last, 0));
+        launch_filter_ingest(n, s, d_rays, f, geo.p, fil.p, live(), queue(), scene.ctr.p);
+        return RT_OK;
+    }
+    int closest_filtered(const float *d_rays, const rt_ray_filter &f, int n, const rt_hit_out &out, hipStream_t s) {
+        int rc = begin_filtered(d_rays, f, n, s);
+        if (rc) return rc;
+        launch_filtered_closest(counters, std::min(blocks_for(n), blocks), s, scene.ds, geo.p, fil.p,
+                                has_masks ? masks.p : nullptr, live(), queue(), hits.p, overflow.p, scene.ctr.p);
+        hipLaunchKernelGGL(query_hit_egest_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, s, hits.p, geo.p, (uint32_t)n,
+                           scene.ds.spheres, scene.ds.tris, scene.ds.mat_idx, scene.ds.sphere_count, out, scene.ctr.p);
+        return end(6, n, s);
+    }
+    int occluded_filtered(const float *d_rays, const rt_ray_filter &f, int n, uint8_t *d_occ, hipStream_t s) {
+        int rc = begin_filtered(d_rays, f, n, s);
+        if (rc) return rc;
+        launch_filtered_anyhit(counters, std::min(blocks_for(n), blocks), s, scene.ds, geo.p, fil.p,
+                               has_masks ? masks.p : nullptr, live(), queue(), d_occ, overflow.p, scene.ctr.p);
+        return end(7, n, s);
+    }
+    // The primitive mask words: a copy on s into the object's buffer, in the event chain like an update.
+    int set_masks(const uint32_t *m, bool on_host, hipStream_t s) {
+        HIPCHK(hipSetDevice(scene.device));
+        if (pending) HIPCHK(hipStreamWaitEvent(s, last, 0));
+        if (m && prim_count)
+            HIPCHK(hipMemcpyAsync(masks.p, m, (size_t)prim_count * sizeof(uint32_t),
+                                  on_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
+        has_masks = m != nullptr && prim_count > 0;
+        int rc = end(0, 0, s);
+        if (rc || !on_host) return rc;
+        HIPCHK(hipStreamSynchronize(s));
+        return RT_OK;
+    }
+    // Stages the host filter's members behind the rays; d receives the device pointers.
+    int stage_filter(const float *rays, const rt_ray_filter &f, int n, rt_ray_filter &d) {
+        hipStream_t s = stream;
+        if ((size_t)n > host_filter_cap) {
+            HIPCHK(hipSetDevice(scene.device));
+            const size_t want = std::max<size_t>({(size_t)n, 2 * host_filter_cap, (size_t)kBlock});
+            host_filter_cap = 0;            // the host calls are blocking: nothing reads the old staging
+            int rc;
+            if ((rc = s_tmin.alloc(want)) || (rc = s_skip.alloc(want)) || (rc = s_rmask.alloc(want))) return rc;
+            host_filter_cap = want;
+        }
+        const size_t m = (size_t)n;
+        d = rt_ray_filter{};
+        HIPCHK(hipMemcpyAsync(s_rays.p, rays, m * 6 * sizeof(float), hipMemcpyHostToDevice, s));
+        if (f.tmin) {
+            HIPCHK(hipMemcpyAsync(s_tmin.p, f.tmin, m * sizeof(float), hipMemcpyHostToDevice, s));
+            d.tmin = s_tmin.p;
+        }
+        if (f.tmax) {
+            HIPCHK(hipMemcpyAsync(s_tmax.p, f.tmax, m * sizeof(float), hipMemcpyHostToDevice, s));
+            d.tmax = s_tmax.p;
+        }
+        if (f.skip) {
+            HIPCHK(hipMemcpyAsync(s_skip.p, f.skip, m * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            d.skip = s_skip.p;
+        }
+        if (f.mask) {
+            HIPCHK(hipMemcpyAsync(s_rmask.p, f.mask, m * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+            d.mask = s_rmask.p;
+        }
+        return RT_OK;
+    }
+    int closest_filtered_host(const float *rays, const rt_ray_filter &f, int n, const rt_hit_out &out) {
+        int rc = reserve_host_hit(n);
+        if (rc) return rc;
+        hipStream_t s = stream;
+        rt_ray_filter df{};
+        if ((rc = stage_filter(rays, f, n, df))) return rc;
+        rt_hit_out d{};
+        if (out.t) d.t = s_t.p;
+        if (out.index) d.index = s_index.p;
+        if (out.uv) d.uv = s_hit.p;
+        if (out.normal) d.normal = s_hit.p + 2 * host_hit_cap;
+        if (out.position) d.position = s_hit.p + 5 * host_hit_cap;
+        if (out.material) d.material = s_mat.p;
+        if (out.front_face) d.front_face = s_occ.p;
+        if ((rc = closest_filtered(s_rays.p, df, n, d, s))) return rc;
+        const size_t m = (size_t)n;
+        if (out.t) HIPCHK(hipMemcpyAsync(out.t, d.t, m * sizeof(float), hipMemcpyDeviceToHost, s));
+        if (out.index) HIPCHK(hipMemcpyAsync(out.index, d.index, m * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        if (out.uv) HIPCHK(hipMemcpyAsync(out.uv, d.uv, m * 2 * sizeof(float), hipMemcpyDeviceToHost, s));
+        if (out.normal) HIPCHK(hipMemcpyAsync(out.normal, d.normal, m * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
+        if (out.position) HIPCHK(hipMemcpyAsync(out.position, d.position, m * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
+        if (out.material) HIPCHK(hipMemcpyAsync(out.material, d.material, m * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        if (out.front_face) HIPCHK(hipMemcpyAsync(out.front_face, d.front_face, m, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return RT_OK;
+    }
+    int occluded_filtered_host(const float *rays, const rt_ray_filter &f, int n, uint8_t *occ) {
+        int rc = reserve_host(n);
+        if (rc) return rc;
+        hipStream_t s = stream;
+        rt_ray_filter df{};
+        if ((rc = stage_filter(rays, f, n, df))) return rc;
+        if ((rc = occluded_filtered(s_rays.p, df, n, s_occ.p, s))) return rc;
+        HIPCHK(hipMemcpyAsync(occ, s_occ.p, (size_t)n, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         return RT_OK;
     }
@@ -1201,6 +1324,63 @@ int rt_query_nearest_k_host(rt_query *q, const float *points, const float *max_d
     const int rc = nearest_k_args("rt_query_nearest_k_host", q, points, n, k, out);
     if (rc) return rc > 0 ? RT_OK : rc;
     return q->nearest_k_host(points, max_dist, n, k, *out);
+}
+
+// The checks shared by the four filtered calls; > 0: n == 0, nothing to do.
+static int filtered_args(const char *fn, const rt_query *q, const void *rays, int32_t n, const void *out) {
+    const std::string f(fn);
+    if (!q) return rtamd::fail(RT_E_INVALID, f + ": null query object");
+    if (n < 0) return rtamd::fail(RT_E_INVALID, f + ": negative ray count");
+    if (n == 0) return 1;
+    if (!rays || !out) return rtamd::fail(RT_E_INVALID, f + ": null pointer");
+    return RT_OK;
+}
+
+int rt_query_closest_filtered(rt_query *q, const float *d_rays, const rt_ray_filter *d_filter, int32_t n,
+                              const rt_hit_out *d_out, void *hip_stream) {
+    const int rc = filtered_args("rt_query_closest_filtered", q, d_rays, n, d_out);
+    if (rc) return rc > 0 ? RT_OK : rc;
+    return q->closest_filtered(d_rays, d_filter ? *d_filter : rt_ray_filter{}, n, *d_out, static_cast<hipStream_t>(hip_stream));
+}
+
+int rt_query_occluded_filtered(rt_query *q, const float *d_rays, const rt_ray_filter *d_filter, int32_t n,
+                               uint8_t *d_occluded, void *hip_stream) {
+    const int rc = filtered_args("rt_query_occluded_filtered", q, d_rays, n, d_occluded);
+    if (rc) return rc > 0 ? RT_OK : rc;
+    return q->occluded_filtered(d_rays, d_filter ? *d_filter : rt_ray_filter{}, n, d_occluded,
+                                static_cast<hipStream_t>(hip_stream));
+}
+
+int rt_query_closest_filtered_host(rt_query *q, const float *rays, const rt_ray_filter *filter, int32_t n,
+                                   const rt_hit_out *out) {
+    const int rc = filtered_args("rt_query_closest_filtered_host", q, rays, n, out);
+    if (rc) return rc > 0 ? RT_OK : rc;
+    return q->closest_filtered_host(rays, filter ? *filter : rt_ray_filter{}, n, *out);
+}
+
+int rt_query_occluded_filtered_host(rt_query *q, const float *rays, const rt_ray_filter *filter, int32_t n,
+                                    uint8_t *occluded) {
+    const int rc = filtered_args("rt_query_occluded_filtered_host", q, rays, n, occluded);
+    if (rc) return rc > 0 ? RT_OK : rc;
+    return q->occluded_filtered_host(rays, filter ? *filter : rt_ray_filter{}, n, occluded);
+}
+
+int rt_query_set_masks(rt_query *q, const uint32_t *d_masks, int32_t count, void *hip_stream) {
+    if (!q) return rtamd::fail(RT_E_INVALID, "rt_query_set_masks: null query object");
+    if (count != q->prim_count)
+        return rtamd::fail(RT_E_INVALID, "rt_query_set_masks: count " + std::to_string(count) +
+                                             " is not the scene's sphere_count + triangle_count = " +
+                                             std::to_string(q->prim_count));
+    return q->set_masks(d_masks, false, static_cast<hipStream_t>(hip_stream));
+}
+
+int rt_query_set_masks_host(rt_query *q, const uint32_t *masks, int32_t count) {
+    if (!q) return rtamd::fail(RT_E_INVALID, "rt_query_set_masks_host: null query object");
+    if (count != q->prim_count)
+        return rtamd::fail(RT_E_INVALID, "rt_query_set_masks_host: count " + std::to_string(count) +
+                                             " is not the scene's sphere_count + triangle_count = " +
+                                             std::to_string(q->prim_count));
+    return q->set_masks(masks, true, q->stream);
 }
 
 int rt_query_stats(rt_query *q, rt_stats *stats) {

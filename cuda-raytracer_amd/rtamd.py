@@ -164,6 +164,54 @@ def _nearest_k_args(k, fields):
     return int(k), tuple(f for f in NEAREST_K_FIELDS if f in names)
 
 
+class RtRayFilter(C.Structure):
+    """rt_ray_filter: tmin (n) float32, tmax (n) float32, skip (n) int32, mask (n) uint32; every pointer optional."""
+    _fields_ = [(n, P) for n in ("tmin", "tmax", "skip", "mask")]
+
+
+RAY_FILTER_DTYPES = {"tmin": np.float32, "tmax": np.float32, "skip": np.int32, "mask": np.uint32}
+
+
+def _filter_np(n, **members):
+    """The filter members given as numpy (None = not given): each a contiguous array of shape (n,) of its dtype, nothing
+    converted.  Returns (RtRayFilter, the arrays to keep alive)."""
+    keep = {}
+    for name, dt in RAY_FILTER_DTYPES.items():
+        v = members.get(name)
+        if v is None:
+            continue
+        if _is_tensor(v):
+            raise ValueError("%s must be a numpy array when rays is one" % name)
+        a = np.asarray(v)
+        if a.dtype != dt or a.shape != (n,) or not a.flags["C_CONTIGUOUS"]:
+            raise ValueError("%s must be a contiguous %s array of shape (n,)" % (name, np.dtype(dt).name))
+        keep[name] = a
+    return RtRayFilter(**{k: _ptr(a) for k, a in keep.items()}), keep
+
+
+def _masks_np(masks, count):
+    """Primitive mask words given as numpy: a contiguous uint32 array of sphere_count + triangle_count words."""
+    a = np.asarray(masks)
+    if a.dtype != np.uint32 or a.ndim != 1 or not a.flags["C_CONTIGUOUS"]:
+        raise ValueError("masks must be a contiguous 1-D uint32 array, not %s %s" % (a.dtype, a.shape))
+    if a.shape[0] != count:
+        raise ValueError("masks must have sphere_count + triangle_count = %d words, not %d" % (count, a.shape[0]))
+    return a
+
+
+def masks_from_materials(scene, table):
+    """Primitive mask words from materials: table[material_indices] as uint32, one word per primitive in the public
+    numbering (spheres first).  table: one word per material of the scene (any integer array-like)."""
+    t = np.asarray(table)
+    if t.ndim != 1 or t.dtype.kind not in "iu":
+        raise ValueError("table must be a 1-D integer array, not %s %s" % (t.dtype, t.shape))
+    if t.shape[0] < scene.view.material_count:
+        raise ValueError("table must have one word per material (%d), not %d" % (scene.view.material_count, t.shape[0]))
+    if t.size and (t.min() < 0 or t.max() > 0xFFFFFFFF):
+        raise ValueError("table words must fit uint32")
+    return np.ascontiguousarray(t.astype(np.uint32)[scene.arrays()["material_indices"]])
+
+
 def _points_np(points):
     a = np.asarray(points)
     if a.dtype != np.float32:
@@ -423,6 +471,41 @@ class Scene:
         count-only multi_hit on this host scene, no GPU."""
         return _signed_distance(self, points, direction)
 
+    def _filtered_args(self, rays, tmin, tmax, skip, mask, masks):
+        a = RayQuery._rays_np(rays)
+        n = a.shape[0]
+        rf, keep = _filter_np(n, tmin=tmin, tmax=tmax, skip=skip, mask=mask)
+        m = None if masks is None else _masks_np(masks, self.view.sphere_count + self.view.triangle_count)
+        return a, n, rf, keep, m
+
+    def closest_filtered(self, rays, tmin=None, tmax=None, skip=None, mask=None, fields=("t", "index"), masks=None,
+                         stats=False):
+        """rt_scene_closest_filtered: the host twin of RayQuery.closest_filtered, no GPU: rays (n, 6)
+        float32, the filter members None or (n,) arrays (tmin, tmax float32, skip int32, mask uint32) and masks None
+        or sphere_count + triangle_count uint32 words, numpy and contiguous.  Returns a dict of the requested hit-record
+        fields, bit for bit what the device call writes (the fields past t and index through hit_records); with
+        stats=True a pair (dict, the walk's counters as a dict)."""
+        names = _hit_fields(fields)
+        a, n, rf, keep, m = self._filtered_args(rays, tmin, tmax, skip, mask, masks)
+        t, idx = np.zeros(n, np.float32), np.zeros(n, np.int32)
+        st = RtStats()
+        f = lib().rt_scene_closest_filtered
+        f.argtypes = [P, P, P, P, I32, P, P, P]
+        _check(f(self.ptr, _ptr(m) if m is not None else None, _ptr(a), C.byref(rf), n, _ptr(t), _ptr(idx), C.byref(st)))
+        out = self.hit_records(a, t, idx, names) if set(names) - {"t", "index"} else {k: {"t": t, "index": idx}[k] for k in names}
+        return (out, st.as_dict()) if stats else out
+
+    def occluded_filtered(self, rays, tmin=None, tmax=None, skip=None, mask=None, masks=None, stats=False):
+        """rt_scene_occluded_filtered: the host twin of RayQuery.occluded_filtered, no GPU; arguments as
+        closest_filtered's.  Returns a bool mask; with stats=True a pair (mask, the walk's counters as a dict)."""
+        a, n, rf, keep, m = self._filtered_args(rays, tmin, tmax, skip, mask, masks)
+        occ = np.zeros(n, np.uint8)
+        st = RtStats()
+        f = lib().rt_scene_occluded_filtered
+        f.argtypes = [P, P, P, P, I32, P, P]
+        _check(f(self.ptr, _ptr(m) if m is not None else None, _ptr(a), C.byref(rf), n, _ptr(occ), C.byref(st)))
+        return (occ.view(np.bool_), st.as_dict()) if stats else occ.view(np.bool_)
+
     def arrays(self):
         v = self.view
 
@@ -612,7 +695,8 @@ class RayQuery:
     under the same rules; closest_point(points, max_dist=None) is the point query (nearest surface point, distance,
     index, uv), nearest_k(points, k, max_dist=None) the range query (every primitive within max_dist, the k nearest in
     order with their count) and signed_distance closest_point's composition with the crossing parity; update(vertices) moves the triangles under
-    the frozen BVH topology."""
+    the frozen BVH topology.  closest_filtered and occluded_filtered are closest_hit and occluded over the surfaces a
+    per-ray filter lets count (tmin, tmax, skip, mask against the primitive mask words of set_masks)."""
 
     def __init__(self, scene, device=0, counters=False, L=None):
         self.L = L or lib()
@@ -847,6 +931,121 @@ class RayQuery:
         f.rt_query_nearest_k_host.argtypes = [P, P, P, I32, I32, P]
         _check(f.rt_query_nearest_k_host(self.h, _ptr(a), _ptr(md) if md is not None else None, n, k, C.byref(no)), f)
         return out
+
+    @staticmethod
+    def _check_member_tensor(x, device, what, dtypes):
+        """check_tensor's rules for a per-ray filter member or the mask words: a 1-D contiguous tensor on
+        cuda:<device> of one of the torch dtypes named in `dtypes`; returns its length."""
+        import torch
+        if not _is_tensor(x):
+            raise ValueError("%s must be a torch.Tensor when rays is one" % what)
+        allowed = [getattr(torch, d) for d in dtypes if hasattr(torch, d)]
+        if x.dtype not in allowed:
+            raise ValueError("%s must be %s, not %s" % (what, " or ".join(dtypes), x.dtype))
+        if x.dim() != 1:
+            raise ValueError("%s must have shape (n), not %s" % (what, tuple(x.shape)))
+        if not x.is_contiguous():
+            raise ValueError("%s must be contiguous" % what)
+        if x.device.type != "cuda" or x.device.index != int(device):
+            raise ValueError("%s must be on cuda:%d, not %s" % (what, int(device), x.device))
+        return int(x.shape[0])
+
+    _FILTER_TORCH = {"tmin": ("float32",), "tmax": ("float32",), "skip": ("int32",), "mask": ("uint32", "int32")}
+
+    def _filter_tensors(self, n, **members):
+        """The filter members given as tensors (None = not given), validated; an int32 mask is read as its bits."""
+        ptrs = {}
+        for name, dtypes in self._FILTER_TORCH.items():
+            v = members.get(name)
+            if v is None:
+                continue
+            if self._check_member_tensor(v, self.device, name, dtypes) != n:
+                raise ValueError("%s must have one entry per ray" % name)
+            ptrs[name] = v.data_ptr()
+        return RtRayFilter(**ptrs)
+
+    def set_masks(self, masks):
+        """rt_query_set_masks: the primitive mask words, one uint32 per primitive in the public numbering (spheres
+        first), or None to drop them (every primitive's word is then 0xFFFFFFFF).  A numpy uint32 array goes through
+        the _host call (blocking); a torch.Tensor on cuda:<device> (uint32, or int32 read as its bits) is copied on
+        torch.cuda.current_stream(device) without any synchronisation: calls enqueued earlier see the old masks, later
+        ones the new.  The masks survive update().  Anything else raises ValueError."""
+        f = self.L
+        count = self.scene.view.sphere_count + self.scene.view.triangle_count if self.scene is not None else None
+        if masks is None:
+            f.rt_query_set_masks_host.argtypes = [P, P, I32]
+            _check(f.rt_query_set_masks_host(self.h, None, count), f)
+            return
+        if _is_tensor(masks):
+            import torch
+            n = self._check_member_tensor(masks, self.device, "masks", ("uint32", "int32"))
+            if count is not None and n != count:
+                raise ValueError("masks must have sphere_count + triangle_count = %d words, not %d" % (count, n))
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            f.rt_query_set_masks.argtypes = [P, P, I32, P]
+            _check(f.rt_query_set_masks(self.h, P(masks.data_ptr()), n, P(stream) if stream else None), f)
+            return
+        a = np.asarray(masks)
+        a = _masks_np(a, a.shape[0] if count is None and a.ndim == 1 else count)
+        f.rt_query_set_masks_host.argtypes = [P, P, I32]
+        _check(f.rt_query_set_masks_host(self.h, _ptr(a), a.shape[0]), f)
+
+    def closest_filtered(self, rays, tmin=None, tmax=None, skip=None, mask=None, fields=("t", "index")):
+        """rt_query_closest_filtered: the closest hit among the surfaces that count for each ray: hits in
+        [max(tmin, 0.005), min(tmax, 1e30)), not on primitive skip, on a primitive whose mask word (set_masks) shares a
+        bit with the ray's `mask`.  Every member is None or one entry per ray (tmin, tmax float32, skip int32, mask
+        uint32).  Returns a dict of the requested hit-record fields as closest_hit does (a miss has t 1e30, index -1);
+        fields=() only traverses and counts.  The walk visits the near child first and is part of the call's
+        definition; with no filter it need not return closest()'s index where two surfaces tie in t.  Tensors in
+        (the members then tensors too), tensors out on torch.cuda.current_stream(device) without any synchronisation; a
+        numpy array takes the _host path (blocking) and gives numpy.  Anything malformed raises ValueError."""
+        names = _hit_fields(fields)
+        f = self.L
+        if _is_tensor(rays):
+            import torch
+            n = self.check_tensor(rays, self.device)
+            rf = self._filter_tensors(n, tmin=tmin, tmax=tmax, skip=skip, mask=mask)
+            dt = {np.float32: torch.float32, np.int32: torch.int32, np.uint8: torch.bool}
+            out = {k: torch.empty((n,) + HIT_SHAPES[k][0], dtype=dt[HIT_SHAPES[k][1]], device=rays.device) for k in names}
+            ho = RtHitOut(**{k: v.data_ptr() for k, v in out.items()})
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            f.rt_query_closest_filtered.argtypes = [P, P, P, I32, P, P]
+            _check(f.rt_query_closest_filtered(self.h, P(rays.data_ptr()), C.byref(rf), n, C.byref(ho),
+                                               P(stream) if stream else None), f)
+            return out
+        a = self._rays_np(rays)
+        n = a.shape[0]
+        rf, keep = _filter_np(n, tmin=tmin, tmax=tmax, skip=skip, mask=mask)
+        out = {k: np.zeros((n,) + HIT_SHAPES[k][0], HIT_SHAPES[k][1]) for k in names}
+        ho = RtHitOut(**{k: _ptr(v) for k, v in out.items()})
+        f.rt_query_closest_filtered_host.argtypes = [P, P, P, I32, P]
+        _check(f.rt_query_closest_filtered_host(self.h, _ptr(a), C.byref(rf), n, C.byref(ho)), f)
+        if "front_face" in out:
+            out["front_face"] = out["front_face"].view(np.bool_)
+        return out
+
+    def occluded_filtered(self, rays, tmin=None, tmax=None, skip=None, mask=None):
+        """rt_query_occluded_filtered: whether any surface that counts for the ray (closest_filtered's filter) lies in
+        its interval: a bool mask, equal to closest_filtered's index >= 0 under the same filter.  Arguments and paths
+        as closest_filtered's."""
+        f = self.L
+        if _is_tensor(rays):
+            import torch
+            n = self.check_tensor(rays, self.device)
+            rf = self._filter_tensors(n, tmin=tmin, tmax=tmax, skip=skip, mask=mask)
+            occ = torch.empty(n, dtype=torch.bool, device=rays.device)
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            f.rt_query_occluded_filtered.argtypes = [P, P, P, I32, P, P]
+            _check(f.rt_query_occluded_filtered(self.h, P(rays.data_ptr()), C.byref(rf), n, P(occ.data_ptr()),
+                                                P(stream) if stream else None), f)
+            return occ
+        a = self._rays_np(rays)
+        n = a.shape[0]
+        rf, keep = _filter_np(n, tmin=tmin, tmax=tmax, skip=skip, mask=mask)
+        occ = np.zeros(n, np.uint8)
+        f.rt_query_occluded_filtered_host.argtypes = [P, P, P, I32, P]
+        _check(f.rt_query_occluded_filtered_host(self.h, _ptr(a), C.byref(rf), n, _ptr(occ)), f)
+        return occ.view(np.bool_)
 
     def signed_distance(self, points, direction=(0.5773503, 0.5773503, 0.5773503)):
         """closest_point's distance, negated where the point lies inside a closed mesh: a point is taken to be inside

@@ -603,6 +603,94 @@ int rt_query_nearest_k_host(rt_query *q, const float *points, const float *max_d
 int rt_scene_nearest_k(const rt_scene *scene, const float *points, const float *max_dist, int32_t n, int32_t k,
                        const rt_nearest_k_out *out);
 
+/* Filtered ray queries: the closest hit and the any-hit answer over the surfaces the caller lets count -- a per-ray
+ * interval, one primitive to skip and visibility masks.  The presence of these symbols is the feature
+ * probe; RT_ABI_VERSION and every existing struct are unchanged.  No reference counterpart as an interface; every
+ * geometric predicate restates the reference's traversal.
+ * All arithmetic is float32, each operation rounded once, no contraction.  S = the scene's sphere count, T its
+ * triangle count; primitives are numbered as everywhere (spheres first, then S + triangle).
+ * rt_ray_filter: one optional array of n entries per member (NULL = not given); a NULL struct behaves as a struct of
+ * NULLs.  For ray i:
+ *   lower bound  lo = tmin[i] > kEps ? tmin[i] : kEps, kEps = 0.005 as a float (0x1.47ae16p-8): NULL, NaN, negative and
+ *                small values give kEps, the unfiltered calls' behaviour; with +inf nothing is accepted.
+ *   upper bound  B by rt_query_occluded's rule: tmax[i] where tmax[i] <= 1e30, otherwise (larger, +inf, NaN, NULL) 1e30.
+ *   masks        the object holds an optional array M of S + T uint32 words in the primitive numbering
+ *                (rt_query_set_masks); with none set every primitive's word is 0xFFFFFFFF.  The ray's word is
+ *                rm = mask ? mask[i] : 0xFFFFFFFF.
+ *   eligible(p)  (p != skip[i]) && ((M[p] & rm) != 0).  A skip value that names no primitive, and a NULL skip, exclude
+ *                nothing; rm = 0 excludes everything.
+ *   triangle j   accepted under a bound c iff the reference's test (scene.cu:160-195) accepts with closest = c, giving
+ *                t, and !(t < lo), and eligible(S + j).  Because lo >= kEps this equals the reference's test with kEps
+ *                replaced by lo.
+ *   sphere k     the reference's test (scene.cu:340-371) with kEps replaced by lo: the near root t = mhb - hs if
+ *                t < c && !(t < lo), otherwise the far root t = mhb + hs under the same test; accepted iff one of them
+ *                passes and eligible(k).  A lo between the two roots therefore returns the far root.  With lo = kEps
+ *                this is the reference's test bit for bit.  host/ray_filter_math.h is the only statement of it.
+ * rt_query_occluded_filtered is rt_query_occluded's definition with these acceptance tests: `closest` is held at B, the
+ * root is entered iff !(0 >= B), a child iff its box is hit with tmax = B and !(entry >= B), and the answer is 1 iff
+ * some primitive is accepted.  Eligibility depends on the ray and the primitive alone and the bound is held, so which
+ * nodes are entered does not depend on the visit order and neither does the answer -- rt_query_occluded's argument,
+ * unchanged.  With a NULL filter and no masks it is rt_query_occluded bit for bit, counters included.
+ * rt_query_closest_filtered has a pinned walk of its own, part of the call's definition (the bound shrinks, so the order
+ * matters, as for rt_query_closest; unlike that call the near child goes first).  State closest = B, index = -1.
+ *   1. spheres 0..S-1 in order, each tested under the current closest; an accepted one sets closest = t, index = k;
+ *   2. if 0 >= closest the ray ends (no node is entered), otherwise the root is entered;
+ *   3. leaf: its triangles [child2, child1) in order under the current closest; an accepted one sets closest = t,
+ *      index = S + j; the exhausted leaf pops;
+ *   4. internal node: ray_aabb_intersection (scene.cu:109-132) of child1, then of child2, with tmax = closest; a child is
+ *      entered iff it is hit and !(entry >= closest); child2 goes first iff it is entered and (child1 is not, or
+ *      t2 < t1) -- a tie goes to child1; the selected child is entered and, if both are entered, the other one is
+ *      pushed with its entry distance; with neither entered, pop;
+ *   5. pop: an empty stack ends the ray; an entry whose stored distance >= the current closest is discarded and the walk
+ *      pops again; otherwise it is entered.
+ * Result: (closest, index), and (1e30, -1) when nothing was accepted.  A NaN follows the predicates literally, as in
+ * the reference: an accepted NaN t becomes closest.  The walk pushes at most one entry per level.
+ * Relations, under one filter and one set of masks:
+ *   R1  index >= 0 <=> rt_query_occluded_filtered == 1: until its first accept the walk's bound is B and it enters
+ *       exactly the nodes the any-hit walk enters.
+ *   R2  a hit (t, index) is a member of the brute-force set {p eligible, accepted under the bound B}.
+ *   R3  it is NOT promised to be that set's minimum, nor, with an empty filter, rt_query_closest's answer: a box's float
+ *       entry distance can exceed the float t of a triangle inside it, either shrinking-bound walk then prunes the box,
+ *       and the two walks break exact-t ties by their own visit order (DESIGN §17 has the measured counts).
+ * rt_query_set_masks copies count = S + T words from a device pointer into a buffer of the object on hip_stream and
+ * joins the event chain: calls enqueued earlier see the old masks, later ones the new; NULL drops the masks (count is
+ * still checked).  The masks survive rt_query_update_triangles.  After it, with no query since, rt_query_stats returns
+ * zeros.  The _host variant takes a host pointer and blocks.
+ * The two query calls follow every rule of rt_query_multi_hit: device pointers on q's device, enqueued on hip_stream,
+ * they join the event chain, allocate nothing once the scratch holds n rays and never wait on the host; d_filter and
+ * d_out are host structs of device pointers, read before the call returns; the geometry is the object's current
+ * resident geometry.  rt_query_closest_filtered writes any field of rt_hit_out, all optional, the record being
+ * rt_query_closest_hit's of the filtered (t, index).  n == 0 is RT_OK and touches no pointer; a null object or scene,
+ * n < 0, null rays or a null output with n > 0, or a count other than S + T is RT_E_INVALID before any HIP call.
+ * rt_query_stats after them reports as after rt_query_closest and rt_query_occluded; with collect_counters Pn (nodes
+ * entered), Iv, Tt and sphere_tests are those of the pinned walks, exact on every ray (the any-hit walk stops at its
+ * first accept, the closest one tests every sphere).
+ * The _host variants take host pointers throughout (the filter's members too), stage through buffers of the object and
+ * block.  rt_scene_closest_filtered and rt_scene_occluded_filtered are the host twins: the same walks over rt_scene.bvh
+ * on a host scene, no GPU, bit for bit the device's output; masks = S + T host words or NULL; stats (optional) receives
+ * live_segments, hits, misses, hits_sphere (closest) and the four counters.  The hit-record fields of a filtered hit
+ * on the host are rt_scene_hit_records applied to the twin's (t, index). */
+typedef struct {            /* every pointer optional: NULL = not given */
+    const float    *tmin;   /* n */
+    const float    *tmax;   /* n */
+    const int32_t  *skip;   /* n */
+    const uint32_t *mask;   /* n */
+} rt_ray_filter;
+int rt_query_set_masks(rt_query *q, const uint32_t *d_masks /* NULL: none */, int32_t count, void *hip_stream);
+int rt_query_set_masks_host(rt_query *q, const uint32_t *masks, int32_t count);
+int rt_query_closest_filtered(rt_query *q, const float *d_rays, const rt_ray_filter *d_filter, int32_t n,
+                              const rt_hit_out *d_out, void *hip_stream);
+int rt_query_occluded_filtered(rt_query *q, const float *d_rays, const rt_ray_filter *d_filter, int32_t n,
+                               uint8_t *d_occluded, void *hip_stream);
+int rt_query_closest_filtered_host(rt_query *q, const float *rays, const rt_ray_filter *filter, int32_t n,
+                                   const rt_hit_out *out);
+int rt_query_occluded_filtered_host(rt_query *q, const float *rays, const rt_ray_filter *filter, int32_t n,
+                                    uint8_t *occluded);
+int rt_scene_closest_filtered(const rt_scene *scene, const uint32_t *masks, const float *rays,
+                              const rt_ray_filter *filter, int32_t n, float *t, int32_t *index, rt_stats *stats);
+int rt_scene_occluded_filtered(const rt_scene *scene, const uint32_t *masks, const float *rays,
+                               const rt_ray_filter *filter, int32_t n, uint8_t *occluded, rt_stats *stats);
+
 /* Replaces the bloom block of main (raytracing.cu:356-393, kernels :21-74): high-pass
  * (luminance > threshold), clamped box blur of `radius` horizontally then vertically,
  * add back.  fb is a host W*H*3 buffer, updated in place. */
