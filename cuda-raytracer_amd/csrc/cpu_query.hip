@@ -13,10 +13,13 @@
 // And rt_scene_closest_filtered / rt_scene_occluded_filtered, the host twins of the filtered ray queries:
 // the pinned near-first walk with the shrinking bound and the any-hit walk with the bound held, the filter's
 // arithmetic from ray_filter_math.h.
+// And rt_scene_hemisphere, the host twin of rt_query_hemisphere, and rt_hemisphere_rays: the sample
+// generator of hemisphere_math.h over the filtered any-hit twin.
 #include "rt_abi.h"
 #include "rt_device.h"
 #include "closest_point_math.h"
 #include "ray_filter_math.h"
+#include "hemisphere_math.h"
 
 #include <algorithm>
 #include <cstring>
@@ -343,6 +346,68 @@ extern "C" int rt_scene_occluded_filtered(const rt_scene *s, const uint32_t *mas
         hits += occ;
     }
     fill_stats(stats, n, w, hits, 0);
+    return RT_OK;
+}
+
+// rt_scene_hemisphere, the host twin of rt_query_hemisphere: the generator of hemisphere_math.h, which
+// hemisphere_kernel compiles too, and the filtered any-hit twin above, per work item.
+extern "C" int rt_scene_hemisphere(const rt_scene *s, const uint32_t *masks, const float *frames, const rt_ray_filter *filter,
+                                   int32_t n, const rt_hemisphere_params *params, const rt_hemisphere_out *out,
+                                   rt_stats *stats) {
+    namespace hemi = rtamd::hemi;
+    const std::string f("rt_scene_hemisphere");
+    if (!s) return rtamd::fail(RT_E_INVALID, f + ": null scene");
+    if (n < 0) return rtamd::fail(RT_E_INVALID, f + ": negative point count");
+    if (n == 0) return RT_OK;
+    if (!frames) return rtamd::fail(RT_E_INVALID, f + ": null frames");
+    if (const char *why = hemi::params_error(params, n)) return rtamd::fail(RT_E_INVALID, f + ": " + why);
+    if (!out || (!out->open_count && !out->openness)) return rtamd::fail(RT_E_INVALID, f + ": no output pointer");
+    if (s->bvh_node_count < 1 || !s->bvh) return rtamd::fail(RT_E_INVALID, f + ": scene has no BVH root");
+    const uint32_t ns = (uint32_t)params->samples;
+    std::vector<int32_t> stack;
+    Work w;
+    uint64_t hits = 0;
+    for (int32_t i = 0; i < n; i++) {
+        const float *r = frames + (size_t)i * 6;
+        const V3 p = v3(r[0], r[1], r[2]), nh = hemi::unit_normal(v3(r[3], r[4], r[5]));
+        const Filter fl = filter_of(filter, masks, i);
+        uint32_t open = 0;
+        for (uint32_t k = 0; k < ns; k++) {
+            const V3 d = hemi::direction(nh, hemi::work_item(params->point_offset, (uint32_t)i, ns, k), params->seed, params->mode);
+            open += occluded_filtered(*s, fl, p, d, w, stack) ? 0u : 1u;
+        }
+        hits += ns - open;
+        if (out->open_count) out->open_count[i] = (int32_t)open;
+        if (out->openness) out->openness[i] = (float)open / (float)ns;
+    }
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        const uint64_t rays = (uint64_t)n * ns;
+        stats->live_segments = rays;
+        stats->nodes_popped = w.pn; stats->internal_visits = w.iv; stats->triangle_tests = w.tt; stats->sphere_tests = w.st;
+        stats->hits = hits; stats->misses = rays - hits;
+    }
+    return RT_OK;
+}
+
+extern "C" int rt_hemisphere_rays(const float *frames, int32_t n, const rt_hemisphere_params *params, float *rays_out) {
+    namespace hemi = rtamd::hemi;
+    const std::string f("rt_hemisphere_rays");
+    if (n < 0) return rtamd::fail(RT_E_INVALID, f + ": negative point count");
+    if (n == 0) return RT_OK;
+    if (!frames || !rays_out) return rtamd::fail(RT_E_INVALID, f + ": null pointer");
+    if (const char *why = hemi::params_error(params, n)) return rtamd::fail(RT_E_INVALID, f + ": " + why);
+    const uint32_t ns = (uint32_t)params->samples;
+    for (int32_t i = 0; i < n; i++) {
+        const float *r = frames + (size_t)i * 6;
+        const V3 nh = hemi::unit_normal(v3(r[3], r[4], r[5]));
+        for (uint32_t k = 0; k < ns; k++) {
+            const V3 d = hemi::direction(nh, hemi::work_item(params->point_offset, (uint32_t)i, ns, k), params->seed, params->mode);
+            float *o = rays_out + ((size_t)i * ns + k) * 6;
+            o[0] = r[0]; o[1] = r[1]; o[2] = r[2];
+            o[3] = d.x; o[4] = d.y; o[5] = d.z;
+        }
+    }
     return RT_OK;
 }
 

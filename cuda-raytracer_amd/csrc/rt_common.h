@@ -247,4 +247,15 @@ void launch_filtered_anyhit(bool count, int grid, hipStream_t s, const DevScene 
                             const uint32_t *masks, const uint32_t *live, uint32_t *queue, uint8_t *out, uint32_t *overflow,
                             Counters *ctr);
 
+// hemisphere_kernel (hemisphere.hip) for rt_query.hip: the ingest of n frames and their filter into `geo`
+// (the unit normal in the direction's place), `fil` and `count` (zeroed), starting the queue with live_count = n * S
+// work items; the traversal, which adds each point's escaped sample rays to count[i]; and the egest of the counts.
+int hemisphere_blocks_per_cu(int &per_cu);
+void launch_hemisphere_ingest(int n, hipStream_t s, const float *d_frames, const rt_ray_filter &f, uint32_t live_count,
+                              float4 *geo, uint2 *fil, uint32_t *count, uint32_t *live, uint32_t *queue, Counters *ctr);
+void launch_hemisphere(bool count_work, int grid, hipStream_t s, const DevScene &ds, const float4 *geo, const uint2 *fil,
+                       const uint32_t *masks, const uint32_t *live, uint32_t *queue, uint32_t *count,
+                       const rt_hemisphere_params &p, uint32_t *overflow, Counters *ctr);
+void launch_hemisphere_egest(int n, hipStream_t s, const uint32_t *count, int32_t samples, const rt_hemisphere_out &out);
+
 }  // namespace rtamd

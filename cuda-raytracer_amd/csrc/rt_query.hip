@@ -3,12 +3,14 @@
 // and its C ABI.
 // The closest-hit traversal is the renderer's trace_kernel, compiled in rt_render.hip and launched through
 // rt_common.h, as are the closest-point traversal of closest_point.hip and the nearest-k one of
-// nearest_k.hip and the filtered ray queries' ingest and traversals of ray_filter.hip; the
-// refit of rt_query_update_triangles is bvh_refit.hip.
+// nearest_k.hip and the filtered ray queries' ingest and traversals of ray_filter.hip and the
+// hemisphere query's kernels of hemisphere.hip; the refit of rt_query_update_triangles is bvh_refit.hip
+// (DESIGN §12).
 #include "rt_common.h"
 #include "bvh_refit.h"
 #include "bvh_refit_math.h"
 #include "hit_record_math.h"
+#include "hemisphere_math.h"
 
 #include <algorithm>
 #include <cstring>
@@ -671,7 +673,7 @@ struct rt_query {
     hipEvent_t last = nullptr;
     bool pending = false;             // `last` has been recorded
     int last_kind = 0;                // 0 none (an update, set_masks), 1 closest, 2 occluded, 3 multi_hit, 4 closest_point,
-                                      // 5 nearest_k, 6 closest_filtered, 7 occluded_filtered
+                                      // 5 nearest_k, 6 closest_filtered, 7 occluded_filtered, 8 hemisphere
     int32_t last_n = 0;
     rtamd::RefitPlan plan;            // rt_query_update_triangles: level tables, built in init
 
@@ -694,20 +696,21 @@ struct rt_query {
         HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         int rc = scene.init(sc, o->device, stream);
         if (rc) return rc;
-        int per_cu_c = 0, per_cu_a = 0, per_cu_m = 0, per_cu_p = 0, per_cu_n = 0, per_cu_fc = 0, per_cu_fa = 0;
+        int per_cu_c = 0, per_cu_a = 0, per_cu_m = 0, per_cu_p = 0, per_cu_n = 0, per_cu_fc = 0, per_cu_fa = 0, per_cu_h = 0;
         if ((rc = trace_closest_blocks_per_cu(per_cu_c)) || (rc = closest_point_blocks_per_cu(per_cu_p)) ||
-            (rc = nearest_k_blocks_per_cu(per_cu_n)) || (rc = ray_filter_blocks_per_cu(per_cu_fc, per_cu_fa)))
+            (rc = nearest_k_blocks_per_cu(per_cu_n)) || (rc = ray_filter_blocks_per_cu(per_cu_fc, per_cu_fa)) ||
+            (rc = hemisphere_blocks_per_cu(per_cu_h)))
             return rc;
         HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_a, anyhit_kernel<false>, kBlock, 0));
         HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_m, multihit_kernel<false>, kBlock, 0));
-        blocks = std::max(1, scene.cus * std::max({1, per_cu_c, per_cu_a, per_cu_m, per_cu_p, per_cu_n, per_cu_fc, per_cu_fa}));
+        blocks = std::max(1, scene.cus * std::max({1, per_cu_c, per_cu_a, per_cu_m, per_cu_p, per_cu_n, per_cu_fc, per_cu_fa, per_cu_h}));
         prim_count = sc->sphere_count + sc->triangle_count;
         if ((rc = masks.alloc((size_t)prim_count))) return rc;
         HIPCHK(hipEventCreateWithFlags(&last, hipEventDisableTiming));
         if ((rc = words.alloc((size_t)(1 + kQueues) * kQueueStride))) return rc;
         if ((rc = plan.build(sc, scene.node_rec, stream))) return rc;
         // trace_kernel and filtered_closest_kernel: 2 words (ref, distance) for each of kStackMax - kStackLds entries
-        // per lane; the any-hit, multi-hit, nearest-k and filtered any-hit kernels' kStackMax - kAnyStackLds one-word
+        // per lane; the any-hit, multi-hit, nearest-k, filtered any-hit and hemisphere kernels' kStackMax - kAnyStackLds one-word
         // entries fit in the same buffer
         return overflow.alloc((size_t)blocks * kBlock * 2 * (kStackMax - kStackLds));
     }
@@ -952,6 +955,40 @@ struct rt_query {
         launch_filtered_anyhit(counters, std::min(blocks_for(n), blocks), s, scene.ds, geo.p, fil.p,
                                has_masks ? masks.p : nullptr, live(), queue(), d_occ, overflow.p, scene.ctr.p);
         return end(7, n, s);
+    }
+    // The hemisphere query: hemisphere.hip's ingest, traversal and egest in the scratch of the ray queries,
+    // one slot and one filter row per point; the points' counts live in the first word of their `hits` records, so the
+    // scratch grows with n, not with n * S.  p and out: checked by hemisphere_args.
+    int hemisphere(const float *d_frames, const rt_ray_filter &f, int n, const rt_hemisphere_params &p,
+                   const rt_hemisphere_out &out, hipStream_t s) {
+        HIPCHK(hipSetDevice(scene.device));
+        int rc = reserve(n);
+        if (rc) return rc;
+        if (pending) HIPCHK(hipStreamWaitEvent(s, last, 0));
+        const int64_t work = (int64_t)n * p.samples;
+        uint32_t *count = reinterpret_cast<uint32_t *>(hits.p);
+        launch_hemisphere_ingest(n, s, d_frames, f, (uint32_t)work, geo.p, fil.p, count, live(), queue(), scene.ctr.p);
+        launch_hemisphere(counters, std::min(blocks_for(work), blocks), s, scene.ds, geo.p, fil.p,
+                          has_masks ? masks.p : nullptr, live(), queue(), count, p, overflow.p, scene.ctr.p);
+        launch_hemisphere_egest(n, s, count, p.samples, out);
+        return end(8, (int)work, s);
+    }
+    int hemisphere_host(const float *frames, const rt_ray_filter &f, int n, const rt_hemisphere_params &p,
+                        const rt_hemisphere_out &out) {
+        int rc = reserve_host(n);
+        if (rc) return rc;
+        hipStream_t s = stream;
+        rt_ray_filter df{};
+        if ((rc = stage_filter(frames, f, n, df))) return rc;
+        rt_hemisphere_out d{};
+        if (out.open_count) d.open_count = s_index.p;
+        if (out.openness) d.openness = s_t.p;
+        if ((rc = hemisphere(s_rays.p, df, n, p, d, s))) return rc;
+        const size_t m = (size_t)n;
+        if (out.open_count) HIPCHK(hipMemcpyAsync(out.open_count, d.open_count, m * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        if (out.openness) HIPCHK(hipMemcpyAsync(out.openness, d.openness, m * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return RT_OK;
     }
     // The primitive mask words: a copy on s into the object's buffer, in the event chain like an update.
     int set_masks(const uint32_t *m, bool on_host, hipStream_t s) {
@@ -1363,6 +1400,34 @@ int rt_query_occluded_filtered_host(rt_query *q, const float *rays, const rt_ray
     const int rc = filtered_args("rt_query_occluded_filtered_host", q, rays, n, occluded);
     if (rc) return rc > 0 ? RT_OK : rc;
     return q->occluded_filtered_host(rays, filter ? *filter : rt_ray_filter{}, n, occluded);
+}
+
+// The checks shared by the two hemisphere calls; > 0: n == 0, nothing to do.
+static int hemisphere_args(const char *fn, const rt_query *q, const void *frames, int32_t n, const rt_hemisphere_params *p,
+                           const rt_hemisphere_out *out) {
+    const std::string f(fn);
+    if (!q) return rtamd::fail(RT_E_INVALID, f + ": null query object");
+    if (n < 0) return rtamd::fail(RT_E_INVALID, f + ": negative point count");
+    if (n == 0) return 1;
+    if (!frames) return rtamd::fail(RT_E_INVALID, f + ": null frames");
+    if (const char *why = rtamd::hemi::params_error(p, n)) return rtamd::fail(RT_E_INVALID, f + ": " + why);
+    if (!out || (!out->open_count && !out->openness)) return rtamd::fail(RT_E_INVALID, f + ": no output pointer");
+    return RT_OK;
+}
+
+int rt_query_hemisphere(rt_query *q, const float *d_frames, const rt_ray_filter *d_filter, int32_t n,
+                        const rt_hemisphere_params *params, const rt_hemisphere_out *d_out, void *hip_stream) {
+    const int rc = hemisphere_args("rt_query_hemisphere", q, d_frames, n, params, d_out);
+    if (rc) return rc > 0 ? RT_OK : rc;
+    return q->hemisphere(d_frames, d_filter ? *d_filter : rt_ray_filter{}, n, *params, *d_out,
+                         static_cast<hipStream_t>(hip_stream));
+}
+
+int rt_query_hemisphere_host(rt_query *q, const float *frames, const rt_ray_filter *filter, int32_t n,
+                             const rt_hemisphere_params *params, const rt_hemisphere_out *out) {
+    const int rc = hemisphere_args("rt_query_hemisphere_host", q, frames, n, params, out);
+    if (rc) return rc > 0 ? RT_OK : rc;
+    return q->hemisphere_host(frames, filter ? *filter : rt_ray_filter{}, n, *params, *out);
 }
 
 int rt_query_set_masks(rt_query *q, const uint32_t *d_masks, int32_t count, void *hip_stream) {

@@ -189,6 +189,72 @@ def _filter_np(n, **members):
     return RtRayFilter(**{k: _ptr(a) for k, a in keep.items()}), keep
 
 
+class RtHemisphereParams(C.Structure):
+    """rt_hemisphere_params: samples, mode (0 cosine, 1 uniform), seed, point_offset."""
+    _fields_ = [("samples", I32), ("mode", I32), ("seed", C.c_uint32), ("point_offset", C.c_uint32)]
+
+
+class RtHemisphereOut(C.Structure):
+    """rt_hemisphere_out: open_count (n) int32, openness (n) float32; every pointer optional."""
+    _fields_ = [(n, P) for n in ("open_count", "openness")]
+
+
+HEMISPHERE_MAX_SAMPLES = 4096   # RT_HEMISPHERE_MAX_SAMPLES
+HEMISPHERE_MODES = {"cosine": 0, "uniform": 1}
+HEMISPHERE_FIELDS = tuple(n for n, _ in RtHemisphereOut._fields_)
+HEMISPHERE_DTYPES = {"open_count": np.int32, "openness": np.float32}
+
+
+def _hemisphere_params(n, samples, mode, seed, point_offset):
+    """RtHemisphereParams of the Python arguments, or ValueError: samples an int in 1..HEMISPHERE_MAX_SAMPLES with
+    n * samples <= 2^31 - 1, mode a name of HEMISPHERE_MODES, seed and point_offset ints in 0..2^32 - 1."""
+    if isinstance(samples, bool) or not isinstance(samples, (int, np.integer)):
+        raise ValueError("samples must be an integer, not %s" % type(samples).__name__)
+    if not 1 <= int(samples) <= HEMISPHERE_MAX_SAMPLES:
+        raise ValueError("samples must be in 1..%d, not %d" % (HEMISPHERE_MAX_SAMPLES, int(samples)))
+    if mode not in HEMISPHERE_MODES:
+        raise ValueError("unknown mode %r (known: %s)" % (mode, ", ".join(HEMISPHERE_MODES)))
+    for name, v in (("seed", seed), ("point_offset", point_offset)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= 0xFFFFFFFF:
+            raise ValueError("%s must be an integer in 0..2^32 - 1, not %r" % (name, v))
+    if n * int(samples) > 0x7FFFFFFF:
+        raise ValueError("n * samples = %d does not fit int32" % (n * int(samples)))
+    return RtHemisphereParams(int(samples), HEMISPHERE_MODES[mode], int(seed), int(point_offset))
+
+
+def _hemisphere_fields(fields):
+    """The requested outputs in HEMISPHERE_FIELDS order (at least one); an unknown name raises ValueError."""
+    names = (fields,) if isinstance(fields, str) else tuple(fields)
+    for k in names:
+        if k not in HEMISPHERE_DTYPES:
+            raise ValueError("unknown hemisphere field %r (known: %s)" % (k, ", ".join(HEMISPHERE_FIELDS)))
+    if not names:
+        raise ValueError("fields must name at least one of %s" % ", ".join(HEMISPHERE_FIELDS))
+    return tuple(k for k in HEMISPHERE_FIELDS if k in names)
+
+
+def _frames_np(points, normals):
+    """points and normals (n, 3) float32 numpy -> frames (n, 6) float32, contiguous."""
+    p = _points_np(points)
+    nm = np.asarray(normals)
+    if nm.dtype != np.float32 or nm.shape != p.shape:
+        raise ValueError("normals must be float32 of points' shape (n, 3), not %s %s" % (nm.dtype, nm.shape))
+    return np.ascontiguousarray(np.hstack([p, nm]))
+
+
+def hemisphere_rays(points, normals, samples, mode="cosine", seed=0, point_offset=0):
+    """rt_hemisphere_rays: the n * samples sample rays (n * samples, 6) float32 that a hemisphere call with these
+    arguments stands for, row i * samples + s = (points[i], direction of sample s); numpy, host only, no scene."""
+    fr = _frames_np(points, normals)
+    n = fr.shape[0]
+    hp = _hemisphere_params(n, samples, mode, seed, point_offset)
+    rays = np.zeros((n * hp.samples, 6), np.float32)
+    f = lib().rt_hemisphere_rays
+    f.argtypes = [P, I32, P, P]
+    _check(f(_ptr(fr), n, C.byref(hp), _ptr(rays)))
+    return rays
+
+
 def _masks_np(masks, count):
     """Primitive mask words given as numpy: a contiguous uint32 array of sphere_count + triangle_count words."""
     a = np.asarray(masks)
@@ -506,6 +572,26 @@ class Scene:
         _check(f(self.ptr, _ptr(m) if m is not None else None, _ptr(a), C.byref(rf), n, _ptr(occ), C.byref(st)))
         return (occ.view(np.bool_), st.as_dict()) if stats else occ.view(np.bool_)
 
+    def hemisphere(self, points, normals, samples, mode="cosine", seed=0, point_offset=0, tmin=None, tmax=None, skip=None,
+                   mask=None, fields=HEMISPHERE_FIELDS, masks=None, stats=False):
+        """rt_scene_hemisphere: the host twin of RayQuery.hemisphere, no GPU: points and normals (n, 3)
+        float32, the filter members None or (n,) arrays, one row per point, and masks None or sphere_count +
+        triangle_count uint32 words, numpy and contiguous.  Returns a dict of the requested fields, bit for bit what
+        the device call writes; with stats=True a pair (dict, the walks' counters summed over all n * samples rays)."""
+        names = _hemisphere_fields(fields)
+        fr = _frames_np(points, normals)
+        n = fr.shape[0]
+        hp = _hemisphere_params(n, samples, mode, seed, point_offset)
+        rf, keep = _filter_np(n, tmin=tmin, tmax=tmax, skip=skip, mask=mask)
+        m = None if masks is None else _masks_np(masks, self.view.sphere_count + self.view.triangle_count)
+        out = {k: np.zeros(n, HEMISPHERE_DTYPES[k]) for k in names}
+        ho = RtHemisphereOut(**{k: _ptr(v) for k, v in out.items()})
+        st = RtStats()
+        f = lib().rt_scene_hemisphere
+        f.argtypes = [P, P, P, P, I32, P, P, P]
+        _check(f(self.ptr, _ptr(m) if m is not None else None, _ptr(fr), C.byref(rf), n, C.byref(hp), C.byref(ho), C.byref(st)))
+        return (out, st.as_dict()) if stats else out
+
     def arrays(self):
         v = self.view
 
@@ -696,7 +782,10 @@ class RayQuery:
     index, uv), nearest_k(points, k, max_dist=None) the range query (every primitive within max_dist, the k nearest in
     order with their count) and signed_distance closest_point's composition with the crossing parity; update(vertices) moves the triangles under
     the frozen BVH topology.  closest_filtered and occluded_filtered are closest_hit and occluded over the surfaces a
-    per-ray filter lets count (tmin, tmax, skip, mask against the primitive mask words of set_masks)."""
+    per-ray filter lets count (tmin, tmax, skip, mask against the primitive mask words of set_masks).
+    hemisphere(points, normals, samples) counts, per surface point, the sample rays over the hemisphere above it that
+    escape (made on the device, walked as occluded_filtered walks them), and ambient_occlusion is its openness in cosine
+    mode."""
 
     def __init__(self, scene, device=0, counters=False, L=None):
         self.L = L or lib()
@@ -1046,6 +1135,55 @@ class RayQuery:
         f.rt_query_occluded_filtered_host.argtypes = [P, P, P, I32, P]
         _check(f.rt_query_occluded_filtered_host(self.h, _ptr(a), C.byref(rf), n, _ptr(occ)), f)
         return occ.view(np.bool_)
+
+    def hemisphere(self, points, normals, samples, mode="cosine", seed=0, point_offset=0, tmin=None, tmax=None, skip=None,
+                   mask=None, fields=HEMISPHERE_FIELDS):
+        """rt_query_hemisphere: how open the hemisphere above each surface point is.  points and normals
+        (n, 3) float32; `samples` rays per point (1..4096) are made on the device from (seed, point_offset + i, s) --
+        mode "cosine" (cosine-weighted about the normal) or "uniform" -- and walked as occluded_filtered walks them
+        under the point's filter row: tmin, tmax (the AO radius), skip (the point's own primitive), mask against the
+        set_masks words, each None or one entry per point.  Returns a dict of the requested fields: open_count (n,)
+        int32, the rays that escaped, and openness (n,) float32 = open_count / samples.  The counts are exactly
+        reproducible; a batch split into parts called with point_offset = the part's first row gives the whole
+        batch's rows; hemisphere_rays() returns the rays a call stands for.  Tensors in (the members then tensors too),
+        tensors out on torch.cuda.current_stream(device) without any synchronisation; numpy takes the _host path
+        (blocking) and gives numpy.  Anything malformed raises ValueError before the library is called."""
+        names = _hemisphere_fields(fields)
+        f = self.L
+        if _is_tensor(points):
+            import torch
+            if not _is_tensor(normals):
+                raise ValueError("normals must be a torch.Tensor when points is one")
+            n = self.check_tensor(points, self.device, "points", (3,))
+            if self.check_tensor(normals, self.device, "normals", (3,)) != n:
+                raise ValueError("normals must have one row per point")
+            hp = _hemisphere_params(n, samples, mode, seed, point_offset)
+            rf = self._filter_tensors(n, tmin=tmin, tmax=tmax, skip=skip, mask=mask)
+            frames = torch.cat([points, normals], 1)
+            dt = {np.float32: torch.float32, np.int32: torch.int32}
+            out = {k: torch.empty(n, dtype=dt[HEMISPHERE_DTYPES[k]], device=points.device) for k in names}
+            ho = RtHemisphereOut(**{k: v.data_ptr() for k, v in out.items()})
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            f.rt_query_hemisphere.argtypes = [P, P, P, I32, P, P, P]
+            _check(f.rt_query_hemisphere(self.h, P(frames.data_ptr()), C.byref(rf), n, C.byref(hp), C.byref(ho),
+                                         P(stream) if stream else None), f)
+            return out
+        if _is_tensor(normals):
+            raise ValueError("normals must be a numpy array when points is one")
+        fr = _frames_np(points, normals)
+        n = fr.shape[0]
+        hp = _hemisphere_params(n, samples, mode, seed, point_offset)
+        rf, keep = _filter_np(n, tmin=tmin, tmax=tmax, skip=skip, mask=mask)
+        out = {k: np.zeros(n, HEMISPHERE_DTYPES[k]) for k in names}
+        ho = RtHemisphereOut(**{k: _ptr(v) for k, v in out.items()})
+        f.rt_query_hemisphere_host.argtypes = [P, P, P, I32, P, P]
+        _check(f.rt_query_hemisphere_host(self.h, _ptr(fr), C.byref(rf), n, C.byref(hp), C.byref(ho)), f)
+        return out
+
+    def ambient_occlusion(self, points, normals, samples, radius=None, skip=None, seed=0):
+        """hemisphere's openness in cosine mode: 1 = nothing within `radius` (None or one float32 per point; None =
+        unbounded) above the point, 0 = fully enclosed.  skip: each point's own primitive, or None."""
+        return self.hemisphere(points, normals, samples, "cosine", seed, 0, tmax=radius, skip=skip, fields=("openness",))["openness"]
 
     def signed_distance(self, points, direction=(0.5773503, 0.5773503, 0.5773503)):
         """closest_point's distance, negated where the point lies inside a closed mesh: a point is taken to be inside

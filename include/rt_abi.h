@@ -691,6 +691,60 @@ int rt_scene_closest_filtered(const rt_scene *scene, const uint32_t *masks, cons
 int rt_scene_occluded_filtered(const rt_scene *scene, const uint32_t *masks, const float *rays,
                                const rt_ray_filter *filter, int32_t n, uint8_t *occluded, rt_stats *stats);
 
+/* Hemisphere visibility queries: how many of S sample rays over the hemisphere above a surface point escape -- ambient
+ * occlusion, sky visibility, lightmap and probe baking.  The presence of these symbols is the feature probe;
+ * RT_ABI_VERSION and every existing struct are unchanged.  No reference counterpart as an interface; the sample
+ * generator is built from the reference's pcg, random_on_sphere and normalise, the walk is rt_query_occluded_filtered's.
+ * Inputs: frames, n rows of 6 floats {p.xyz, nrm.xyz} (a ray's layout); an optional rt_ray_filter of n entries, row i
+ * applying to every sample of point i (skip keeps a point on a surface off its own triangle, tmax is the AO radius; NULL
+ * = the defaults); params: samples = S in 1..RT_HEMISPHERE_MAX_SAMPLES with n * S <= 2^31 - 1, mode, seed, point_offset.
+ * The sample ray of work item (i, s), 0 <= s < S; all arithmetic float32, each operation rounded once, no contraction;
+ * host/hemisphere_math.h is the only statement of it:
+ *   nh  = normalise(nrm) = (1.0f / sqrtf(magsq(nrm))) * nrm; a zero or non-finite normal gives what the arithmetic gives;
+ *   w   = (point_offset + i) * S + s in uint32 arithmetic (it wraps);
+ *   rng = pcg_seed(w * 0x9E3779B1u + seed * 0x85EBCA6Bu);  u = random_on_sphere(rng);
+ *   RT_HEMISPHERE_COSINE   v = nh + u, m = magsq(v), dir = !(m >= 0x1p-40f) ? nh : (1.0f / sqrtf(m)) * v;
+ *   RT_HEMISPHERE_UNIFORM  dir = dot(u, nh) < 0 ? -u : u;
+ *   the ray is (p, dir).
+ * point_offset lets a caller split a batch: rows [a, b) called with point_offset = a give the whole batch's rows.
+ * Answer: open_count[i] = the number of point i's S rays for which rt_query_occluded_filtered's definition, under filter
+ * row i and the object's masks, answers 0 (int32); openness[i] = (float)open_count[i] / (float)S by IEEE division.  Both
+ * are optional members of rt_hemisphere_out.  The count is an integer and the any-hit answer does not depend on the
+ * visit order, so the result is exactly reproducible.
+ * rt_query_hemisphere follows every rule of rt_query_occluded_filtered: device pointers on q's device, enqueued on
+ * hip_stream, it joins the event chain, allocates nothing once the scratch holds n points (rt_query_reserve counts
+ * points: the scratch grows with n, 44 bytes per point, not with n * S) and never waits on the host; d_filter, params and
+ * d_out are host structs, read before the call returns; the geometry and the masks are the object's current ones.
+ * n == 0 is RT_OK and touches no pointer, params included; a null object or scene, n < 0, and with n > 0 null frames,
+ * null params, S outside 1..RT_HEMISPHERE_MAX_SAMPLES, an unknown mode, n * S > 2^31 - 1, or a null out or both outputs
+ * null is RT_E_INVALID with a message before any HIP call.
+ * rt_query_stats after it: live_segments = n * S, hits = occluded samples, misses = escaped samples; with
+ * collect_counters Pn, Iv, Tt and sphere_tests are the pinned any-hit walk's, summed over all n * S rays, exact.
+ * The _host variant takes host pointers throughout, stages through buffers of the object and blocks.
+ * rt_scene_hemisphere is the host twin: the same on a host scene (rt_scene.bvh), no GPU, bit for bit the device's output;
+ * masks = S + T host words or NULL; stats is optional.  rt_hemisphere_rays writes the n * S x 6 sample rays a call stands
+ * for (host only, no scene): row i * S + s = (p_i, dir(i, s)). */
+#define RT_HEMISPHERE_MAX_SAMPLES 4096
+#define RT_HEMISPHERE_COSINE  0
+#define RT_HEMISPHERE_UNIFORM 1
+typedef struct {
+    int32_t  samples;       /* S */
+    int32_t  mode;          /* RT_HEMISPHERE_COSINE or RT_HEMISPHERE_UNIFORM */
+    uint32_t seed;
+    uint32_t point_offset;
+} rt_hemisphere_params;
+typedef struct {            /* every pointer optional: NULL = not written; at least one with n > 0 */
+    int32_t *open_count;    /* n */
+    float   *openness;      /* n */
+} rt_hemisphere_out;
+int rt_query_hemisphere(rt_query *q, const float *d_frames, const rt_ray_filter *d_filter, int32_t n,
+                        const rt_hemisphere_params *params, const rt_hemisphere_out *d_out, void *hip_stream);
+int rt_query_hemisphere_host(rt_query *q, const float *frames, const rt_ray_filter *filter, int32_t n,
+                             const rt_hemisphere_params *params, const rt_hemisphere_out *out);
+int rt_scene_hemisphere(const rt_scene *scene, const uint32_t *masks, const float *frames, const rt_ray_filter *filter,
+                        int32_t n, const rt_hemisphere_params *params, const rt_hemisphere_out *out, rt_stats *stats);
+int rt_hemisphere_rays(const float *frames, int32_t n, const rt_hemisphere_params *params, float *rays_out);
+
 /* Replaces the bloom block of main (raytracing.cu:356-393, kernels :21-74): high-pass
  * (luminance > threshold), clamped box blur of `radius` horizontally then vertically,
  * add back.  fb is a host W*H*3 buffer, updated in place. */
