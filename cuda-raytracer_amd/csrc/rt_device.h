@@ -197,14 +197,17 @@ RT_HD Mat load_mat(const float4 *m) {
 
 // Surface interaction after the closest hit (scene.cu:398-477): emission, rough normal,
 // specular / diffuse / dielectric scatter.  RNG draw order is part of the contract.
-RT_HD void scatter(V3 d, V3 normal, const Mat &m, Rng &rng, V3 &T, V3 &C, V3 &nd) {
+// Returns whether T was multiplied by m.spec (else by m.diffuse).
+RT_HD bool scatter(V3 d, V3 normal, const Mat &m, Rng &rng, V3 &T, V3 &C, V3 &nd) {
+    bool spec;
     C = C + m.emit * T;
     const bool front = dot(normal, d) < 0;
     if (!front) normal = -normal;
     const V3 rough = normalise(normal + m.rough * random_on_sphere(rng));
     const float cos_theta = dot(rough, d);
     if (m.ior == 0) {
-        if (random01(rng) <= m.metal) {
+        spec = random01(rng) <= m.metal;
+        if (spec) {
             T = T * m.spec;
             nd = d - (2 * cos_theta) * rough;
         } else {
@@ -220,7 +223,8 @@ RT_HD void scatter(V3 d, V3 normal, const Mat &m, Rng &rng, V3 &T, V3 &C, V3 &nd
         r0 *= r0;
         const float cs = 1 + cos_theta;
         const float refl = r0 + (1 - r0) * cs * cs * cs * cs * cs;
-        if (sin2 > inv_ior * inv_ior || random01(rng) < refl) {
+        spec = sin2 > inv_ior * inv_ior || random01(rng) < refl;
+        if (spec) {
             T = T * m.spec;
             nd = d - (2 * cos_theta) * rough;
         } else {
@@ -230,6 +234,7 @@ RT_HD void scatter(V3 d, V3 normal, const Mat &m, Rng &rng, V3 &T, V3 &C, V3 &nd
             nd = normalise(par + perp);
         }
     }
+    return spec;
 }
 
 }  // namespace rtd

@@ -192,7 +192,8 @@ __device__ __forceinline__ V3 primary_dir(const DevScene &S, int i, const PassAr
 // do not leave most lanes idle.  Output per slot: {closest t, hit index} (index -1 = miss).
 // The slab pair, the flat triangle test and the leaf refs are rt_common.h's (shared with anyhit_kernel).
 // VSLOT (bounce 1 of the virtual reorder, below): the launch walks every slot of the pass, slot = ray id, and a
-// slot whose bounce-0 bucket (slot_bkt) is kDead is dropped at refill, before anything is counted.
+// slot whose bounce-0 bucket (slot_bkt) is kDead is dropped at refill, before anything is counted; geo holds the slim
+// hand-over's 24-B records {o, d} (shade_kernel<.., SLIM>).
 template <bool SORTED, bool COUNT, int FIRST, bool VSLOT = false>
 __global__ __launch_bounds__(kBlock) RT_TRACE_ATTR void trace_kernel(DevScene S, PassArgs pa, const float4 *__restrict__ geo,
                                                        const uint32_t *__restrict__ live_count,
@@ -390,6 +391,12 @@ __global__ __launch_bounds__(kBlock) RT_TRACE_ATTR void trace_kernel(DevScene S,
                     if (FIRST) {
                         o = S.cam;
                         d = primary_dir(S, (int)first_ray<FIRST>(pa.map, (uint32_t)slot), pa);
+                    } else if (VSLOT) {
+                        // the slim bounce-0 hand-over (shade_kernel<.., SLIM>): 24-B records {o, d}
+                        const float2 *rp = reinterpret_cast<const float2 *>(geo) + (size_t)slot * 3;
+                        const float2 r0 = rp[0], r1 = rp[1], r2 = rp[2];
+                        o = v3(r0.x, r0.y, r1.x);
+                        d = v3(r1.y, r2.x, r2.y);
                     } else {
                         const float4 *rp = geo + (size_t)slot * 2;   // ray state is in slot order
                         const float4 r0 = rp[0];
@@ -527,7 +534,10 @@ struct Shaded {
     uint32_t ray;
     int kind;
     bool acc_holds;                   // acc[ray] holds the radiance of the earlier bounces
+    uint32_t mat;                     // SLIM only: the hit's material index and whether scatter multiplied T by its
+    bool spec;                        // spec (else its diffuse) albedo
 };
+constexpr uint32_t kSpecBit = 0x80;   // slim hand-over: Shaded::spec in a live bounce-0 bucket byte (buckets are 0..64)
 // INLINE (scenes without triangles): the closest hit is the sphere loop (scene.cu:338-372),
 // computed here instead of read from the trace kernel's output.
 // A slot's coalesced inputs (hit record, ray id, seed slot, state), loaded apart from the shading.
@@ -564,9 +574,13 @@ __device__ __forceinline__ ShadeIn shade_in(const PassArgs &pa, int slot, const 
     }
     return in;
 }
-template <bool SORTED, int FIRST, bool INLINE = false>
+// SLIM (bounce 0 of the virtual reorder's slim hand-over): also returns the hit's material index and albedo choice.
+template <bool SORTED, int FIRST, bool INLINE = false, bool SLIM = false>
 __device__ __forceinline__ Shaded shade_from(const DevScene &S, const PassArgs &pa, int slot, const ShadeIn &in,
                                              uint32_t seed_term) {
+    static_assert(!SLIM || FIRST == 1, "the slim hand-over leaves bounce 0, where T enters as (1,1,1)");
+    uint32_t mat = 0;
+    bool spec = false;
     Rng rng = pcg_seed(in.seed * 4137874753u + seed_term);
     float closest = in.h.x;
     int index = __float_as_int(in.h.y);
@@ -619,17 +633,22 @@ __device__ __forceinline__ Shaded shade_from(const DevScene &S, const PassArgs &
         asm volatile("" : "+v"(m0.x), "+v"(m0.y), "+v"(m0.z), "+v"(m0.w), "+v"(m1.x), "+v"(m1.y), "+v"(m1.z),
                           "+v"(m1.w), "+v"(m2.x), "+v"(m2.y), "+v"(m2.z), "+v"(m2.w));
         const Mat m{v3(m0.x, m0.y, m0.z), m0.w, v3(m1.x, m1.y, m1.z), m1.w, v3(m2.x, m2.y, m2.z), m2.w};
-        scatter(d, normal, m, rng, T, C, nd);
+        const bool took_spec = scatter(d, normal, m, rng, T, C, nd);
+        if (SLIM) {                     // T entered as (1,1,1) and left as 1 * m.spec or 1 * m.diffuse
+            spec = took_spec;
+            mat = mi;
+        }
     }
-    return Shaded{no, nd, T, C, ray_id, index == -1 ? 0 : (index < S.sphere_count ? 2 : 1), in.acc_holds};
+    return Shaded{no, nd, T, C, ray_id, index == -1 ? 0 : (index < S.sphere_count ? 2 : 1), in.acc_holds, mat, spec};
 }
-template <bool SORTED, int FIRST, bool INLINE = false>
+template <bool SORTED, int FIRST, bool INLINE = false, bool SLIM = false>
 __device__ __forceinline__ Shaded shade_one(const DevScene &S, const PassArgs &pa, int slot,
                                             const float4 *__restrict__ geo, const float *__restrict__ tz,
                                             const uint32_t *__restrict__ rid, const float2 *__restrict__ hits,
                                             uint32_t seed_term, const uint32_t *__restrict__ seed_of = nullptr) {
-    return shade_from<SORTED, FIRST, INLINE>(S, pa, slot, shade_in<SORTED, FIRST, INLINE>(pa, slot, geo, tz, rid, hits, seed_of),
-                                             seed_term);
+    return shade_from<SORTED, FIRST, INLINE, SLIM>(S, pa, slot,
+                                                   shade_in<SORTED, FIRST, INLINE>(pa, slot, geo, tz, rid, hits, seed_of),
+                                                   seed_term);
 }
 // A nonzero radiance term of this bounce: some component with nonzero magnitude bits (adding +-0 to the
 // radiance so far never changes it: that sum starts at +0 and so is never -0).
@@ -667,7 +686,11 @@ __device__ __forceinline__ unsigned long long match_bucket(uint32_t b, bool vali
 #else
 #define RT_SHADE_ATTR
 #endif
-template <bool SORTED, bool COUNT, int FIRST, bool FUSED, bool INLINE>
+// SLIM (bounce 0 of the virtual reorder, rt_renderer::vre): a surviving ray hands over 27 B instead of 41.  geo holds
+// 24-B records {o, d} (3 x float2 per slot), tz holds one u16 per slot, the hit's material index, and bit 7 of the
+// live bucket byte (kSpecBit) says which albedo scatter took; T and the rid flag are functions of those two
+// (shade_rank_kernel rebuilds them), so no T and no rid is written.
+template <bool SORTED, bool COUNT, int FIRST, bool FUSED, bool INLINE, bool SLIM = false>
 __global__ __launch_bounds__(kBlock) RT_SHADE_ATTR void shade_kernel(DevScene S, PassArgs pa, float4 *__restrict__ geo,
                                                        float *__restrict__ tz, uint32_t *__restrict__ rid,
                                                        float4 *__restrict__ acc, uint8_t *__restrict__ bkt,
@@ -683,13 +706,20 @@ __global__ __launch_bounds__(kBlock) RT_SHADE_ATTR void shade_kernel(DevScene S,
     unsigned hit = 0, miss = 0, hit_sphere = 0;
     // one slot's shading and new state; returns its bucket
     auto shade_slot = [&](int slot) -> uint32_t {
-        const Shaded sh = shade_one<SORTED, FIRST, INLINE>(S, pa, slot, geo, tz, rid, hits, seed_term, seed_of);
+        const Shaded sh = shade_one<SORTED, FIRST, INLINE, SLIM>(S, pa, slot, geo, tz, rid, hits, seed_term, seed_of);
         const V3 no = sh.no, nd = sh.nd, T = sh.T;
         miss += sh.kind == 0;
         hit += sh.kind != 0;
         hit_sphere += sh.kind == 2;
         const bool dead = is_black(T);
-        if (!FUSED && !dead && !last) {     // a terminated ray's geometry is never read again
+        if (SLIM && !dead && !last) {
+            float2 *rec = reinterpret_cast<float2 *>(geo) + (size_t)slot * 3;
+            rec[0] = make_float2(no.x, no.y);
+            rec[1] = make_float2(no.z, nd.x);
+            rec[2] = make_float2(nd.y, nd.z);
+            reinterpret_cast<uint16_t *>(tz)[slot] = (uint16_t)sh.mat;
+        }
+        if (!SLIM && !FUSED && !dead && !last) {     // a terminated ray's geometry is never read again
             geo[(size_t)slot * 2] = make_float4(no.x, no.y, no.z, nd.x);
             geo[(size_t)slot * 2 + 1] = make_float4(nd.y, nd.z, T.x, T.y);
             tz[slot] = T.z;
@@ -717,11 +747,11 @@ __global__ __launch_bounds__(kBlock) RT_SHADE_ATTR void shade_kernel(DevScene S,
         }
         // the flag rides in the ray id, which the reorder moves (at bounce 0 written for every ray: the
         // reorder's bounce-0 scatter reads it there; FUSED: the replay sets it)
-        if (!FUSED && !dead && !last && (FIRST || (term && !sh.acc_holds)))
+        if (!SLIM && !FUSED && !dead && !last && (FIRST || (term && !sh.acc_holds)))
             rid[slot] = sh.ray | (term || sh.acc_holds ? kAccFlag : 0u);
         const uint32_t bk = dead ? kDead : (SORTED ? bucket_of(no, nd, S.min_coord, S.inv_dim) : 0u);
-        if (!last) bkt[slot] = (uint8_t)bk;
-        return bk;
+        if (!last) bkt[slot] = (uint8_t)(bk | (SLIM && !dead && sh.spec ? kSpecBit : 0u));
+        return bk;                      // without kSpecBit: the histogram counts buckets
     };
     if (counts && !last) {
         __shared__ uint32_t h[kBuckets];
@@ -1159,10 +1189,10 @@ __global__ __launch_bounds__(kBlock) RT_REPLAY_ATTR void sort_scatter_shade_kern
 // ---------------------------------------------------------------- virtual bounce-0 reorder
 // Sort on, untiled, a scene with triangles (rt_renderer::vre): the bounce-0 reorder moves nothing.  The reference's
 // sorted position matters to a ray only as the seed of its next shading, and only the rays alive at bounce 2 need
-// to stand in that order.  So bounce 0 shades once in place (shade_kernel, not FUSED: state, bucket, histogram, rid
-// with kAccFlag, all in ray-id order) and sort_scan_kernel gives the bucket runs; bounce 1 traces over the ray-id
-// slots (trace_kernel<.., VSLOT>) and shade_rank_kernel computes each live slot's sorted position with the
-// scatter's own ranking, shades with that position as the seed, and moves only the survivors of bounce 1, to their
+// to stand in that order.  So bounce 0 shades once in place (shade_kernel<.., SLIM>, not FUSED: {o, d}, the hit's
+// material index, bucket + albedo bit, histogram, all in ray-id order) and sort_scan_kernel gives the bucket runs;
+// bounce 1 traces over the ray-id slots (trace_kernel<.., VSLOT>) and shade_rank_kernel computes each live slot's
+// sorted position with the scatter's own ranking, shades with that position as the seed, and moves only the survivors of bounce 1, to their
 // sorted positions of the other buffer set.  The positions of the rays that ended at bounce 1 stay kDead holes of
 // the bounce-1 bucket array (fill_dead_kernel), which the plain reorder that follows drops.
 
@@ -1179,12 +1209,15 @@ __global__ __launch_bounds__(kBlock) void fill_dead_kernel(uint8_t *__restrict__
 // Bounce 1 over the ray-id slots [0, *slot_count): the tiles and rounds of the bounce-0 histogram, the ranking of
 // sort_scatter_kernel on the bounce-0 buckets, shade_kernel's shading and radiance rules with seed = the sorted
 // position.  acc is indexed by ray id = slot, so a terminating ray's add is coalesced.
+// Input is the slim hand-over of shade_kernel<.., SLIM>: the 24-B record {o, d} at geo_in, the bounce-0 hit's
+// material index mat_in[slot] and kSpecBit of the bucket byte.  The rest of the state is rebuilt from the material:
+// T = 1 * (spec or diffuse albedo) is bounce 0's own multiply (scatter, T entering as the laundered (1,1,1)), and
+// rid = slot | kAccFlag iff has_radiance(0 + emit * 1), bounce 0's own term.  Survivors leave with the full state.
 template <bool COUNT>
 __global__ __launch_bounds__(kBlock) RT_SHADE_ATTR void shade_rank_kernel(DevScene S, PassArgs pa,
                                                             const uint8_t *__restrict__ bkt_in,
                                                             const float4 *__restrict__ geo_in,
-                                                            const float *__restrict__ tz_in,
-                                                            const uint32_t *__restrict__ rid_in,
+                                                            const uint16_t *__restrict__ mat_in,
                                                             const float2 *__restrict__ hits, uint32_t seed_term, int last,
                                                             const uint32_t *__restrict__ slot_count, int tiles,
                                                             const uint32_t *__restrict__ offsets,
@@ -1207,10 +1240,20 @@ __global__ __launch_bounds__(kBlock) RT_SHADE_ATTR void shade_rank_kernel(DevSce
         for (int r = 0; r < rounds; r++) {
             const int item = base + r * kBlock + threadIdx.x;
             const bool valid = item < n;
-            const uint32_t b = valid ? bkt_in[item] : 0u;
+            const uint32_t byte = valid ? bkt_in[item] : 0u;
+            const uint32_t b = byte & ~kSpecBit;   // a dead slot is plain kDead
             const bool move = valid && b != kDead;
             ShadeIn in{};
-            if (move) in = shade_in<true, 0, false>(pa, item, geo_in, tz_in, rid_in, hits, nullptr);   // overlaps the ranking
+            float2 r0{}, r1{}, r2{};
+            float4 alb{}, emi{};
+            if (move) {                 // the loads overlap the ranking
+                const float4 *mp = S.mats + (size_t)mat_in[item] * 3;
+                in.h = hits[item];
+                const float2 *rp = reinterpret_cast<const float2 *>(geo_in) + (size_t)item * 3;
+                r0 = rp[0]; r1 = rp[1]; r2 = rp[2];
+                alb = mp[byte & kSpecBit ? 1 : 0];   // {specular, rough} or {diffuse, metal}
+                emi = mp[2];
+            }
             const unsigned long long peers = match_bucket(b, valid);
             const uint32_t rank = rank_below(peers);
             if (valid && rank == 0) wcount[wave][b] = (uint32_t)__popcll(peers);
@@ -1218,6 +1261,16 @@ __global__ __launch_bounds__(kBlock) RT_SHADE_ATTR void shade_rank_kernel(DevSce
             if (move) {
                 uint32_t pos = run[b] + rank;
                 for (int k = 0; k < wave; k++) pos += wcount[k][b];
+                // as in shade_from: the 1 stays opaque, so both products are bounce 0's literal multiplies
+                float one = 1.f;
+                asm volatile("" : "+v"(one));
+                const V3 ones = v3(one, one, one);
+                const V3 T0 = ones * v3(alb.x, alb.y, alb.z);
+                in.r0 = make_float4(r0.x, r0.y, r1.x, r1.y);
+                in.r1 = make_float4(r2.x, r2.y, T0.x, T0.y);
+                in.tz = T0.z;
+                in.ray = (uint32_t)item;
+                in.acc_holds = has_radiance(v3(0, 0, 0) + v3(emi.x, emi.y, emi.z) * ones);
                 in.seed = pos;          // the reference's slot of this ray at bounce 1 (raytracing.cu:89)
                 const Shaded sh = shade_from<true, 0>(S, pa, item, in, seed_term);
                 const V3 no = sh.no, nd = sh.nd, T = sh.T;
@@ -1420,6 +1473,8 @@ struct PassCtx {
     // geo = 2 x float4 {o.xyz, d.x} {d.yz, T.xy}, tz = T.z, rid = the ray's acc index (+ kAccFlag): its ray id,
     // or its home index (Renderer::home).  acc[that] holds {T.z, C}: the radiance once a bounce added a nonzero
     // term, and finally when the ray terminates or after the last bounce.
+    // Renderer::vre, between bounce 0's shade and bounce 1's: geo[0] holds 24-B records {o, d} (3 x float2 per slot),
+    // tz[0] one u16 per slot (the bounce-0 hit's material index), rid[0] nothing (the slim hand-over, shade_kernel).
     DevBuf<float4> geo[2], acc;
     DevBuf<float> tz[2];
     DevBuf<uint32_t> rid[2], sort_counts, sort_offsets, sort_totals, live, queue, overflow;
@@ -1736,7 +1791,9 @@ struct rt_renderer {
             const bool v0 = vre && b == 0, v1 = vre && b == 1;
             const bool fuse_b = !v0 && !v1 && (fused || b <= fused_upto);
             // the shade kernel counts the buckets (bounce 1 of the virtual reorder: sort_hist_kernel, over the sorted positions)
-            uint32_t *hist = shade_hist && !last && !v1 ? c.sort_counts.p : nullptr;
+            // (bounce 0 of it: always the shade kernel, whatever RTAMD_SHADE_HIST says -- its bucket bytes carry
+            // kSpecBit, which sort_hist_kernel does not know)
+            uint32_t *hist = (shade_hist || v0) && !last && !v1 ? c.sort_counts.p : nullptr;
 #define RT_PROCESS3(SORTED, COUNT, FIRST)                                                                        \
     do {                                                                                                         \
         if (!inline_hits)                                                                                        \
@@ -1761,7 +1818,21 @@ struct rt_renderer {
     do {                                                                                                         \
         if (b == 0) RT_PROCESS3(SORTED, COUNT, 1); else RT_PROCESS3(SORTED, COUNT, 0);                           \
     } while (0)
-            if (v1) {
+            if (v0) {
+                // shades in place and hands over slim: 24-B records in geo[cur], material indices in tz[cur] (PassCtx)
+#define RT_V0PROCESS(COUNT)                                                                                      \
+    do {                                                                                                         \
+        hipLaunchKernelGGL((trace_kernel<true, COUNT, 1>), dim3(tgrid), dim3(kBlock), 0, st, scene.ds, pa,       \
+                           c.geo[cur].p, lv, q, c.hits.p, c.overflow.p, scene.ctr.p,                             \
+                           tspan ? tspan + kSpanWords * b : nullptr);                                            \
+        if (em) HIPCHK(hipEventRecord(em, st));                                                                  \
+        hipLaunchKernelGGL((shade_kernel<true, COUNT, 1, false, false, true>), dim3(sgrid), dim3(kBlock), 0, st, \
+                           scene.ds, pa, c.geo[cur].p, c.tz[cur].p, c.rid[cur].p, c.acc.p, c.bkt.p, lv, c.hits.p, \
+                           seed_term, (int)last, scene.ctr.p, nullptr, hist, tiles, 0);                          \
+    } while (0)
+                if (counters) RT_V0PROCESS(true); else RT_V0PROCESS(false);
+#undef RT_V0PROCESS
+            } else if (v1) {
                 // every slot of the pass (live[0]); the state is still in ray-id order, the survivors' new state
                 // goes to their sorted positions of the other buffer set
 #define RT_VPROCESS(COUNT)                                                                                       \
@@ -1771,9 +1842,9 @@ struct rt_renderer {
                            tspan ? tspan + kSpanWords * b : nullptr, c.bkt.p);                                   \
         if (em) HIPCHK(hipEventRecord(em, st));                                                                  \
         hipLaunchKernelGGL((shade_rank_kernel<COUNT>), dim3(sort_grid), dim3(kBlock), 0, st, scene.ds, pa, c.bkt.p, \
-                           c.geo[cur].p, c.tz[cur].p, c.rid[cur].p, c.hits.p, seed_term, (int)last, c.live.p, tiles, \
-                           c.sort_offsets.p, c.sort_totals.p, c.geo[1 - cur].p, c.tz[1 - cur].p, c.rid[1 - cur].p, \
-                           c.bkt1.p, c.acc.p, scene.ctr.p);                                                      \
+                           c.geo[cur].p, reinterpret_cast<const uint16_t *>(c.tz[cur].p), c.hits.p, seed_term,   \
+                           (int)last, c.live.p, tiles, c.sort_offsets.p, c.sort_totals.p, c.geo[1 - cur].p,      \
+                           c.tz[1 - cur].p, c.rid[1 - cur].p, c.bkt1.p, c.acc.p, scene.ctr.p);                   \
     } while (0)
                 if (counters) RT_VPROCESS(true); else RT_VPROCESS(false);
 #undef RT_VPROCESS
