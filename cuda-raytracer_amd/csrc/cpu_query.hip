@@ -15,11 +15,14 @@
 // arithmetic from ray_filter_math.h.
 // And rt_scene_hemisphere, the host twin of rt_query_hemisphere, and rt_hemisphere_rays: the sample
 // generator of hemisphere_math.h over the filtered any-hit twin.
+// And rt_scene_overlap_box, the host twin of rt_query_overlap_box: the set of primitives that meet a box, by
+// box_overlap_math.h, which box_overlap_kernel compiles too.
 #include "rt_abi.h"
 #include "rt_device.h"
 #include "closest_point_math.h"
 #include "ray_filter_math.h"
 #include "hemisphere_math.h"
+#include "box_overlap_math.h"
 
 #include <algorithm>
 #include <cstring>
@@ -160,6 +163,37 @@ void members(const rt_scene &s, rt_vec3 p, float b2, std::vector<Member> &found,
         const bool second = e2 && (!e1 || b < a);      // the nearer child first, a tie to child1: the kernel's order
         if (e1 && e2) stack.push_back(second ? nd.child1 : nd.child2);
         if (e1 || e2) stack.push_back(second ? nd.child2 : nd.child1);
+    }
+}
+
+// rt_scene_overlap_box's set H (rt_abi.h) for one valid box: box_overlap_kernel's walk in its pinned order
+// over the scene's own node array.  first_only: the any-only walk, which stops at the first member.
+void overlapping(const rt_scene &s, rt_vec3 lo, rt_vec3 hi, bool first_only, std::vector<int32_t> &found,
+                 std::vector<int32_t> &stack) {
+    namespace ov = rtamd::ov;
+    found.clear();
+    for (int i = 0; i < s.sphere_count; i++) {
+        if (!ov::sphere_meets(s.spheres[i].center, s.spheres[i].radius, lo, hi)) continue;
+        found.push_back(i);
+        if (first_only) return;
+    }
+    stack.clear();
+    stack.push_back(0);
+    while (!stack.empty()) {
+        const rt_bvh_node &nd = s.bvh[stack.back()];
+        stack.pop_back();
+        if (nd.child2 <= nd.child1) {
+            for (int j = nd.child2; j < nd.child1; j++) {
+                const rt_triangle &tr = s.triangles[j];
+                if (!ov::triangle_meets(tr.p1, tr.p2p1, tr.p3p1, lo, hi)) continue;
+                found.push_back(s.sphere_count + j);
+                if (first_only) return;
+            }
+            continue;
+        }
+        const rt_bvh_node &c1 = s.bvh[nd.child1], &c2 = s.bvh[nd.child2];
+        if (ov::boxes_meet(c2.min_bound, c2.max_bound, lo, hi)) stack.push_back(nd.child2);
+        if (ov::boxes_meet(c1.min_bound, c1.max_bound, lo, hi)) stack.push_back(nd.child1);   // child1 first
     }
 }
 
@@ -407,6 +441,34 @@ extern "C" int rt_hemisphere_rays(const float *frames, int32_t n, const rt_hemis
             o[0] = r[0]; o[1] = r[1]; o[2] = r[2];
             o[3] = d.x; o[4] = d.y; o[5] = d.z;
         }
+    }
+    return RT_OK;
+}
+
+extern "C" int rt_scene_overlap_box(const rt_scene *s, const float *boxes, int32_t n, int32_t k, const rt_overlap_out *out) {
+    namespace ov = rtamd::ov;
+    if (!s) return rtamd::fail(RT_E_INVALID, "rt_scene_overlap_box: null scene");
+    if (n < 0) return rtamd::fail(RT_E_INVALID, "rt_scene_overlap_box: negative box count");
+    if (k < 1 || k > RT_OVERLAP_K_MAX)
+        return rtamd::fail(RT_E_INVALID, "rt_scene_overlap_box: k " + std::to_string(k) + " is outside 1.." +
+                                             std::to_string(RT_OVERLAP_K_MAX));
+    if (n == 0) return RT_OK;
+    if (!boxes || !out) return rtamd::fail(RT_E_INVALID, "rt_scene_overlap_box: null pointer");
+    if ((int64_t)n * k > INT32_MAX)
+        return rtamd::fail(RT_E_INVALID, "rt_scene_overlap_box: n * k = " + std::to_string((int64_t)n * k) + " does not fit int32");
+    if (s->bvh_node_count < 1 || !s->bvh) return rtamd::fail(RT_E_INVALID, "rt_scene_overlap_box: scene has no BVH root");
+    const bool first_only = !out->index && !out->count && out->any;
+    std::vector<int32_t> found, stack;
+    for (int32_t i = 0; i < n; i++) {
+        const float *b = boxes + (size_t)i * 6;
+        const rt_vec3 lo = {b[0], b[1], b[2]}, hi = {b[3], b[4], b[5]};
+        found.clear();
+        if (ov::valid_box(lo, hi)) overlapping(*s, lo, hi, first_only, found, stack);
+        if (out->count) out->count[i] = (int32_t)found.size();
+        if (out->any) out->any[i] = found.empty() ? 0 : 1;
+        if (!out->index) continue;
+        std::sort(found.begin(), found.end());
+        for (int32_t j = 0; j < k; j++) out->index[(size_t)i * k + j] = (size_t)j < found.size() ? found[j] : -1;
     }
     return RT_OK;
 }

@@ -258,4 +258,13 @@ void launch_hemisphere(bool count_work, int grid, hipStream_t s, const DevScene 
                        const rt_hemisphere_params &p, uint32_t *overflow, Counters *ctr);
 void launch_hemisphere_egest(int n, hipStream_t s, const uint32_t *count, int32_t samples, const rt_hemisphere_out &out);
 
+// box_overlap_kernel (box_overlap.hip) for rt_query.hip: the ingest of n boxes into `geo` (two float4 per
+// box: {lo, valid} {hi, 0}) and the traversal; out: device pointers, each optional (index null = nothing kept, only any
+// given = the walk stops at a box's first member).
+int box_overlap_blocks_per_cu(int &per_cu);
+void launch_box_ingest(int n, hipStream_t s, const float *d_boxes, float4 *geo, uint32_t *live, uint32_t *queue,
+                       Counters *ctr);
+void launch_box_overlap(bool count, int grid, hipStream_t s, const DevScene &ds, const float4 *geo, const uint32_t *live,
+                        uint32_t *queue, int k, const rt_overlap_out &out, uint32_t *overflow, Counters *ctr);
+
 }  // namespace rtamd

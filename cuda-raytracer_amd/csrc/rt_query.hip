@@ -673,7 +673,7 @@ struct rt_query {
     hipEvent_t last = nullptr;
     bool pending = false;             // `last` has been recorded
     int last_kind = 0;                // 0 none (an update, set_masks), 1 closest, 2 occluded, 3 multi_hit, 4 closest_point,
-                                      // 5 nearest_k, 6 closest_filtered, 7 occluded_filtered, 8 hemisphere
+                                      // 5 nearest_k, 6 closest_filtered, 7 occluded_filtered, 8 hemisphere, 9 overlap_box
     int32_t last_n = 0;
     rtamd::RefitPlan plan;            // rt_query_update_triangles: level tables, built in init
 
@@ -697,20 +697,21 @@ struct rt_query {
         int rc = scene.init(sc, o->device, stream);
         if (rc) return rc;
         int per_cu_c = 0, per_cu_a = 0, per_cu_m = 0, per_cu_p = 0, per_cu_n = 0, per_cu_fc = 0, per_cu_fa = 0, per_cu_h = 0;
+        int per_cu_o = 0;
         if ((rc = trace_closest_blocks_per_cu(per_cu_c)) || (rc = closest_point_blocks_per_cu(per_cu_p)) ||
             (rc = nearest_k_blocks_per_cu(per_cu_n)) || (rc = ray_filter_blocks_per_cu(per_cu_fc, per_cu_fa)) ||
-            (rc = hemisphere_blocks_per_cu(per_cu_h)))
+            (rc = hemisphere_blocks_per_cu(per_cu_h)) || (rc = box_overlap_blocks_per_cu(per_cu_o)))
             return rc;
         HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_a, anyhit_kernel<false>, kBlock, 0));
         HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_m, multihit_kernel<false>, kBlock, 0));
-        blocks = std::max(1, scene.cus * std::max({1, per_cu_c, per_cu_a, per_cu_m, per_cu_p, per_cu_n, per_cu_fc, per_cu_fa, per_cu_h}));
+        blocks = std::max(1, scene.cus * std::max({1, per_cu_c, per_cu_a, per_cu_m, per_cu_p, per_cu_n, per_cu_fc, per_cu_fa, per_cu_h, per_cu_o}));
         prim_count = sc->sphere_count + sc->triangle_count;
         if ((rc = masks.alloc((size_t)prim_count))) return rc;
         HIPCHK(hipEventCreateWithFlags(&last, hipEventDisableTiming));
         if ((rc = words.alloc((size_t)(1 + kQueues) * kQueueStride))) return rc;
         if ((rc = plan.build(sc, scene.node_rec, stream))) return rc;
         // trace_kernel and filtered_closest_kernel: 2 words (ref, distance) for each of kStackMax - kStackLds entries
-        // per lane; the any-hit, multi-hit, nearest-k, filtered any-hit and hemisphere kernels' kStackMax - kAnyStackLds one-word
+        // per lane; the any-hit, multi-hit, nearest-k, filtered any-hit, hemisphere and box-overlap kernels' kStackMax - kAnyStackLds one-word
         // entries fit in the same buffer
         return overflow.alloc((size_t)blocks * kBlock * 2 * (kStackMax - kStackLds));
     }
@@ -927,6 +928,44 @@ struct rt_query {
         if (out.index) HIPCHK(hipMemcpyAsync(out.index, d.index, m * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         if (out.point) HIPCHK(hipMemcpyAsync(out.point, d.point, m * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
         if (out.count) HIPCHK(hipMemcpyAsync(out.count, d.count, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return RT_OK;
+    }
+    // Every primitive that meets a box, the k smallest indices kept: box_overlap.hip's ingest and traversal in
+    // the scratch of the ray queries (two float4 of geo per box, the same queue words and overflow buffer).  The kernel
+    // keeps each box's list in the caller's index rows; without them nothing is kept.
+    int overlap_box(const float *d_boxes, int n, int k, const rt_overlap_out &out, hipStream_t s) {
+        HIPCHK(hipSetDevice(scene.device));
+        int rc = reserve(n);
+        if (rc) return rc;
+        if (pending) HIPCHK(hipStreamWaitEvent(s, last, 0));
+        launch_box_ingest(n, s, d_boxes, geo.p, live(), queue(), scene.ctr.p);
+        launch_box_overlap(counters, std::min(blocks_for(n), blocks), s, scene.ds, geo.p, live(), queue(), k, out, overflow.p,
+                           scene.ctr.p);
+        return end(9, n, s);
+    }
+    int overlap_box_host(const float *boxes, int n, int k, const rt_overlap_out &out) {
+        int rc = reserve_host(n);
+        if (rc) return rc;
+        const size_t m = (size_t)n * k;
+        if (out.index && m > host_list_cap) {
+            HIPCHK(hipSetDevice(scene.device));
+            const size_t want = std::max(m, 2 * host_list_cap);
+            host_list_cap = 0;              // the host calls are blocking: nothing reads the old staging
+            if ((rc = s_list_t.alloc(want)) || (rc = s_list_i.alloc(want))) return rc;
+            host_list_cap = want;
+        }
+        if (s_count.n < host_cap && (rc = s_count.alloc(host_cap))) return rc;
+        hipStream_t s = stream;
+        rt_overlap_out d{};
+        if (out.index) d.index = s_list_i.p;
+        if (out.count) d.count = s_count.p;
+        if (out.any) d.any = s_occ.p;
+        HIPCHK(hipMemcpyAsync(s_rays.p, boxes, (size_t)n * 6 * sizeof(float), hipMemcpyHostToDevice, s));
+        if ((rc = overlap_box(s_rays.p, n, k, d, s))) return rc;
+        if (out.index) HIPCHK(hipMemcpyAsync(out.index, d.index, m * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        if (out.count) HIPCHK(hipMemcpyAsync(out.count, d.count, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        if (out.any) HIPCHK(hipMemcpyAsync(out.any, d.any, (size_t)n, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         return RT_OK;
     }
@@ -1361,6 +1400,33 @@ int rt_query_nearest_k_host(rt_query *q, const float *points, const float *max_d
     const int rc = nearest_k_args("rt_query_nearest_k_host", q, points, n, k, out);
     if (rc) return rc > 0 ? RT_OK : rc;
     return q->nearest_k_host(points, max_dist, n, k, *out);
+}
+
+// The checks shared by the two box-overlap calls; > 0: n == 0, nothing to do.
+static int overlap_box_args(const char *fn, const rt_query *q, const void *boxes, int32_t n, int32_t k, const void *out) {
+    const std::string f(fn);
+    if (!q) return rtamd::fail(RT_E_INVALID, f + ": null query object");
+    if (n < 0) return rtamd::fail(RT_E_INVALID, f + ": negative box count");
+    if (k < 1 || k > RT_OVERLAP_K_MAX)
+        return rtamd::fail(RT_E_INVALID, f + ": k " + std::to_string(k) + " is outside 1.." + std::to_string(RT_OVERLAP_K_MAX));
+    if (n == 0) return 1;
+    if (!boxes || !out) return rtamd::fail(RT_E_INVALID, f + ": null pointer");
+    if ((int64_t)n * k > INT32_MAX)
+        return rtamd::fail(RT_E_INVALID, f + ": n * k = " + std::to_string((int64_t)n * k) + " does not fit int32");
+    return RT_OK;
+}
+
+int rt_query_overlap_box(rt_query *q, const float *d_boxes, int32_t n, int32_t k, const rt_overlap_out *d_out,
+                         void *hip_stream) {
+    const int rc = overlap_box_args("rt_query_overlap_box", q, d_boxes, n, k, d_out);
+    if (rc) return rc > 0 ? RT_OK : rc;
+    return q->overlap_box(d_boxes, n, k, *d_out, static_cast<hipStream_t>(hip_stream));
+}
+
+int rt_query_overlap_box_host(rt_query *q, const float *boxes, int32_t n, int32_t k, const rt_overlap_out *out) {
+    const int rc = overlap_box_args("rt_query_overlap_box_host", q, boxes, n, k, out);
+    if (rc) return rc > 0 ? RT_OK : rc;
+    return q->overlap_box_host(boxes, n, k, *out);
 }
 
 // The checks shared by the four filtered calls; > 0: n == 0, nothing to do.

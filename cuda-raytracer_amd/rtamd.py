@@ -164,6 +164,44 @@ def _nearest_k_args(k, fields):
     return int(k), tuple(f for f in NEAREST_K_FIELDS if f in names)
 
 
+class RtOverlapOut(C.Structure):
+    """rt_overlap_out: index (n x k) int32, count (n) int32, any (n) uint8; every pointer optional."""
+    _fields_ = [(n, P) for n in ("index", "count", "any")]
+
+
+OVERLAP_K_MAX = 64   # RT_OVERLAP_K_MAX
+OVERLAP_FIELDS = tuple(n for n, _ in RtOverlapOut._fields_)
+OVERLAP_DTYPES = {"index": np.int32, "count": np.int32, "any": np.uint8}
+
+
+def _overlap_shape(field, n, k):
+    return {"index": (n, k), "count": (n,), "any": (n,)}[field]
+
+
+def _overlap_args(k, fields):
+    """k as an int in 1..OVERLAP_K_MAX and the requested fields in OVERLAP_FIELDS order, or ValueError."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise ValueError("k must be an integer, not %s" % type(k).__name__)
+    if not 1 <= int(k) <= OVERLAP_K_MAX:
+        raise ValueError("k must be in 1..%d, not %d" % (OVERLAP_K_MAX, int(k)))
+    names = (fields,) if isinstance(fields, str) else tuple(fields)
+    for f in names:
+        if f not in OVERLAP_DTYPES:
+            raise ValueError("unknown overlap field %r (known: %s)" % (f, ", ".join(OVERLAP_FIELDS)))
+    return int(k), tuple(f for f in OVERLAP_FIELDS if f in names)
+
+
+def _boxes_np(boxes):
+    a = np.asarray(boxes)
+    if a.dtype != np.float32:
+        raise ValueError("boxes must be float32, not %s" % a.dtype)
+    if a.ndim != 2 or a.shape[1] != 6:
+        raise ValueError("boxes must have shape (n, 6), not %s" % (a.shape,))
+    if not a.flags["C_CONTIGUOUS"]:
+        raise ValueError("boxes must be contiguous")
+    return a
+
+
 class RtRayFilter(C.Structure):
     """rt_ray_filter: tmin (n) float32, tmax (n) float32, skip (n) int32, mask (n) uint32; every pointer optional."""
     _fields_ = [(n, P) for n in ("tmin", "tmax", "skip", "mask")]
@@ -532,6 +570,20 @@ class Scene:
         _check(f(self.ptr, _ptr(a), _ptr(md) if md is not None else None, n, k, C.byref(no)))
         return out
 
+    def overlap_box(self, boxes, k, fields=("index", "count")):
+        """rt_scene_overlap_box: the host twin of RayQuery.overlap_box, no GPU: boxes (n, 6) float32
+        {lo.xyz, hi.xyz}, numpy and contiguous.  Returns a dict of the requested fields, bit for bit what the device
+        call writes."""
+        k, names = _overlap_args(k, fields)
+        a = _boxes_np(boxes)
+        n = a.shape[0]
+        out = {f: np.zeros(_overlap_shape(f, n, k), OVERLAP_DTYPES[f]) for f in names}
+        oo = RtOverlapOut(**{f: _ptr(v) for f, v in out.items()})
+        f = lib().rt_scene_overlap_box
+        f.argtypes = [P, P, I32, I32, P]
+        _check(f(self.ptr, _ptr(a), n, k, C.byref(oo)))
+        return out
+
     def signed_distance(self, points, direction=(0.5773503, 0.5773503, 0.5773503)):
         """The host twin of RayQuery.signed_distance (numpy only): the same composition of closest_point and the
         count-only multi_hit on this host scene, no GPU."""
@@ -785,7 +837,8 @@ class RayQuery:
     per-ray filter lets count (tmin, tmax, skip, mask against the primitive mask words of set_masks).
     hemisphere(points, normals, samples) counts, per surface point, the sample rays over the hemisphere above it that
     escape (made on the device, walked as occluded_filtered walks them), and ambient_occlusion is its openness in cosine
-    mode."""
+    mode.  overlap_box(boxes, k) is the volume query: every primitive whose surface meets an axis-aligned box,
+    the k smallest indices, their count and an any flag."""
 
     def __init__(self, scene, device=0, counters=False, L=None):
         self.L = L or lib()
@@ -1019,6 +1072,35 @@ class RayQuery:
         no = RtNearestKOut(**{x: _ptr(v) for x, v in out.items()})
         f.rt_query_nearest_k_host.argtypes = [P, P, P, I32, I32, P]
         _check(f.rt_query_nearest_k_host(self.h, _ptr(a), _ptr(md) if md is not None else None, n, k, C.byref(no)), f)
+        return out
+
+    def overlap_box(self, boxes, k, fields=("index", "count")):
+        """rt_query_overlap_box: for each axis-aligned box {lo.xyz, hi.xyz} every primitive whose surface meets it on the
+        resident geometry.  Returns a dict of the requested fields: index (n, k) int32 -- the min(count, k)
+        smallest member indices ascending (spheres first, then sphere_count + triangle), then -1 --, count (n,) int32,
+        not capped by k, and any (n,) uint8.  1 <= k <= 64.  A box with a non-finite number or lo > hi on an axis meets
+        nothing.  Fields that are not requested are neither written nor allocated; fields=("any",) stops each box's walk
+        at its first member, fields=() only traverses and counts.  boxes (n, 6) float32, contiguous: a torch.Tensor on
+        cuda:<device> gives tensors on torch.cuda.current_stream(device) without any synchronisation; a numpy array
+        takes the _host path (blocking) and gives numpy.  Anything else raises ValueError."""
+        k, names = _overlap_args(k, fields)
+        f = self.L
+        if _is_tensor(boxes):
+            import torch
+            n = self.check_tensor(boxes, self.device, "boxes", shape_tail=(6,))
+            dt = {np.int32: torch.int32, np.uint8: torch.uint8}
+            out = {x: torch.empty(_overlap_shape(x, n, k), dtype=dt[OVERLAP_DTYPES[x]], device=boxes.device) for x in names}
+            oo = RtOverlapOut(**{x: v.data_ptr() for x, v in out.items()})
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            f.rt_query_overlap_box.argtypes = [P, P, I32, I32, P, P]
+            _check(f.rt_query_overlap_box(self.h, P(boxes.data_ptr()), n, k, C.byref(oo), P(stream) if stream else None), f)
+            return out
+        a = _boxes_np(boxes)
+        n = a.shape[0]
+        out = {x: np.zeros(_overlap_shape(x, n, k), OVERLAP_DTYPES[x]) for x in names}
+        oo = RtOverlapOut(**{x: _ptr(v) for x, v in out.items()})
+        f.rt_query_overlap_box_host.argtypes = [P, P, I32, I32, P]
+        _check(f.rt_query_overlap_box_host(self.h, _ptr(a), n, k, C.byref(oo)), f)
         return out
 
     @staticmethod

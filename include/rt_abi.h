@@ -745,6 +745,72 @@ int rt_scene_hemisphere(const rt_scene *scene, const uint32_t *masks, const floa
                         int32_t n, const rt_hemisphere_params *params, const rt_hemisphere_out *out, rt_stats *stats);
 int rt_hemisphere_rays(const float *frames, int32_t n, const rt_hemisphere_params *params, float *rays_out);
 
+/* Box overlap queries: for an axis-aligned box, every primitive whose surface meets it -- the K smallest indices in
+ * order, their count and an any flag: collision broad phase, voxelisation, trigger volumes, region picking.
+ * The presence of these symbols is the feature probe; RT_ABI_VERSION and every existing struct are unchanged.  No
+ * reference counterpart.
+ * All arithmetic is float32, each operation rounded once, no contraction; host/box_overlap_math.h is the only statement
+ * of it.  S = the scene's sphere count; primitives are numbered as everywhere (spheres first, then S + triangle).
+ * boxes: n rows of 6 floats {lo.xyz, hi.xyz}.
+ *   valid box    all six numbers finite and lo.c <= hi.c on every axis.  A box that is not valid has count = 0, any = 0 and
+ *                a row of padding; nothing is tested for it and it adds nothing to the counters.
+ *   surfaces     only surfaces count, as for rt_query_closest_point: a box strictly inside a closed mesh or inside a
+ *                sphere meets nothing.
+ *   node         boxes_meet(nlo, nhi, lo, hi): on every axis nlo.c <= hi.c && lo.c <= nhi.c.  Comparisons only, closed
+ *                (touching counts); the empty-box sentinel meets nothing.
+ *   triangle     (p1, e1 = p2p1, e2 = p3p1), vertices v0 = p1, v1 = p1 + e1, v2 = p1 + e2 (one rounding per component): a
+ *                member iff none of 13 axes separates.  1-3, the box axes: the min / max of the three vertices'
+ *                coordinate c separates iff tmin > hi.c || tmax < lo.c.  4, the plane: m = cross(e1, e2) (each component
+ *                a*b - c*d; not the stored unit normal), s = dot(m, v0) = (m.x*v0.x + m.y*v0.y) + m.z*v0.z,
+ *                bmin = (fminf(m.x*lo.x, m.x*hi.x) + fminf(m.y*lo.y, m.y*hi.y)) + fminf(m.z*lo.z, m.z*hi.z), bmax the same
+ *                with fmaxf; separates iff s < bmin || s > bmax.  5-13, a = edge x unit_i for the edges e1, e2, e2 - e1
+ *                and i = x, y, z in that order for each: with a's two non-zero components (a1, a2) on coordinates
+ *                (c1, c2) -- x: (f.z, -f.y) on (y, z); y: (-f.z, f.x) on (x, z); z: (f.y, -f.x) on (x, y) -- a vertex
+ *                projects to a1*v.c1 + a2*v.c2, the box to [fminf(a1*lo.c1, a1*hi.c1) + fminf(a2*lo.c2, a2*hi.c2), the
+ *                same with fmaxf]; separates iff tmin > bmax || tmax < bmin.  Every separating comparison is strict: a
+ *                NaN never separates, and a zero axis projects everything to 0 and never separates.
+ *   sphere       (c, r): near2 = the closest-point block's box2(c, lo, hi); far2 = (fx*fx + fy*fy) + fz*fz with
+ *                f.c = fmaxf(fabsf(c.c - lo.c), fabsf(hi.c - c.c)); a member iff near2 <= r*r && far2 >= r*r.
+ * H, the set of a valid box: every sphere j is tested, a member with index j; the root is entered; in an entered leaf
+ * every triangle j of [child2, child1) is tested, a member with index S + j; a child is entered iff boxes_meet(child box,
+ * box); nothing stops early.  Every predicate depends on (box, primitive or node) alone, so H is a fixed set whatever
+ * order the nodes are visited in -- rt_query_nearest_k's argument.
+ * Outputs, for a caller-chosen k with 1 <= k <= RT_OVERLAP_K_MAX (every pointer optional, NULL = not written):
+ *   count[i]   |H| as int32, not capped by k;
+ *   any[i]     1 iff |H| >= 1, else 0;
+ *   index      row i holds the min(|H|, k) smallest member indices ascending, then -1.
+ * The any-only walk: with only `any` given (index and count NULL) the walk of a box stops at its first member.  The
+ * answer does not depend on the order; the counters do, so the order is pinned and part of the definition, as
+ * rt_query_occluded's is: spheres in order; the root; in a leaf, triangles in order; at an internal node child1 is
+ * entered if it meets, else child2, and child2 is pushed when both meet; a pop enters the popped node.  The full walk
+ * uses the same order, but its counters do not depend on it.
+ * Relation to brute force (every primitive under triangle / sphere above): H is a subset of that set; a member of it
+ * missing from H has an ancestor node whose box fails boxes_meet.  That can happen by an ulp -- node boxes are grown
+ * from the loaded vertices (and by rt_scene_refit / rt_query_update_triangles from the given ones), while the test sees
+ * p1 + e1 -- and it is the only way the two sets differ.
+ * rt_query_overlap_box follows every rule of rt_query_nearest_k: pointers on q's device, enqueued on hip_stream, joins the
+ * event chain, allocates nothing once the scratch holds n boxes (rt_query_reserve counts boxes) and never waits on the
+ * host; d_out is a host struct of device pointers, read before the call returns; the geometry is the object's current
+ * resident geometry (rt_query_update_triangles).  n == 0 is RT_OK and touches no pointer; a null object (or scene),
+ * n < 0, k outside 1..RT_OVERLAP_K_MAX (checked before n == 0), a null boxes or out pointer with n > 0, or an n * k that
+ * does not fit int32 is RT_E_INVALID before any HIP call.
+ * rt_query_stats after it: live_segments = n, hits = boxes with a member, misses = the rest, hits_sphere = 0; with
+ * collect_counters Pn (nodes entered), Iv, Tt and sphere_tests are those of the walk that ran (the any-only one stops
+ * early), exact in both modes.
+ * The _host variant takes host pointers, stages through buffers of the object and blocks.  rt_scene_overlap_box is the
+ * host twin: the same on a host scene (rt_scene.bvh), no GPU, bit for bit the device's output; it refuses the same bad
+ * arguments. */
+#define RT_OVERLAP_K_MAX 64
+typedef struct {            /* every pointer optional: NULL = not written */
+    int32_t *index;         /* n x k */
+    int32_t *count;         /* n     */
+    uint8_t *any;           /* n     */
+} rt_overlap_out;
+int rt_query_overlap_box(rt_query *q, const float *d_boxes, int32_t n, int32_t k, const rt_overlap_out *d_out,
+                         void *hip_stream);
+int rt_query_overlap_box_host(rt_query *q, const float *boxes, int32_t n, int32_t k, const rt_overlap_out *out);
+int rt_scene_overlap_box(const rt_scene *scene, const float *boxes, int32_t n, int32_t k, const rt_overlap_out *out);
+
 /* Replaces the bloom block of main (raytracing.cu:356-393, kernels :21-74): high-pass
  * (luminance > threshold), clamped box blur of `radius` horizontally then vertically,
  * add back.  fb is a host W*H*3 buffer, updated in place. */
