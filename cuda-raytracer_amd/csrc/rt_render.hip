@@ -193,14 +193,17 @@ __device__ __forceinline__ V3 primary_dir(const DevScene &S, int i, const PassAr
 // The slab pair, the flat triangle test and the leaf refs are rt_common.h's (shared with anyhit_kernel).
 // VSLOT (bounce 1 of the virtual reorder, below): the launch walks every slot of the pass, slot = ray id, and a
 // slot whose bounce-0 bucket (slot_bkt) is kDead is dropped at refill, before anything is counted; geo holds the slim
-// hand-over's 24-B records {o, d} (shade_kernel<.., SLIM>).
+// hand-over's 16-B records {d, t0} (shade_kernel<.., SLIM>), the origin is bounce 0's cam + t0 * primary_dir(slot).
+// Its output is lean: `hits` is a dense array of 4-B hit indices (a miss costs those 4 bytes), and a lane that hit
+// also writes the hit point o + closest * d, shade_from's own expression, as 3 floats at hit_org + 3 * slot.
 template <bool SORTED, bool COUNT, int FIRST, bool VSLOT = false>
 __global__ __launch_bounds__(kBlock) RT_TRACE_ATTR void trace_kernel(DevScene S, PassArgs pa, const float4 *__restrict__ geo,
                                                        const uint32_t *__restrict__ live_count,
                                                        uint32_t *__restrict__ queue, float2 *__restrict__ hits,
                                                        uint32_t *__restrict__ overflow, Counters *__restrict__ ctr,
                                                        unsigned long long *__restrict__ tspan,
-                                                       const uint8_t *__restrict__ slot_bkt = nullptr) {
+                                                       const uint8_t *__restrict__ slot_bkt = nullptr,
+                                                       float *__restrict__ hit_org = nullptr) {
     __shared__ uint2 stack[(kStackLds + 1) * kBlock];   // + one scratch entry per lane
     // tspan (per-launch timing, rt_renderer_set_event_timing): {first wave start, last wave end}
     // on the device's constant-rate wall clock, so a launch's duration excludes the queueing
@@ -218,6 +221,14 @@ __global__ __launch_bounds__(kBlock) RT_TRACE_ATTR void trace_kernel(DevScene S,
     // second half (e' = e - kStackLds), addressed on use (the path is rare; no pointer registers).
     const uint32_t lanes = gridDim.x * kBlock, gl = blockIdx.x * kBlock + threadIdx.x;
     const uint32_t dist_half = lanes * (kStackMax - kStackLds);
+    // VSLOT: the lane's index is put together where the rare path uses it, from an opaque thread index, and is not
+    // kept through the loop: with the refill's primary_dir the kernel otherwise spills it (12 B of scratch)
+    auto overflow_lane = [&]() -> uint32_t {
+        if (!VSLOT) return gl;
+        uint32_t t = threadIdx.x;
+        asm volatile("" : "+v"(t));
+        return blockIdx.x * kBlock + t;
+    };
     const uint32_t L = __builtin_amdgcn_readfirstlane(*live_count);
     const uint32_t waves = gridDim.x * (kBlock / 64);
     const uint32_t chunk = min((uint32_t)kChunkMax, max((uint32_t)kChunkMin, (L / (4 * waves) + 63) & ~63u));
@@ -269,8 +280,8 @@ __global__ __launch_bounds__(kBlock) RT_TRACE_ATTR void trace_kernel(DevScene S,
         // kStackLds is a scratch slot), so the push needs no branch
         col[min(sp, kStackLds) * kBlock] = make_uint2(near_ref, __float_as_uint(near_t));
         if (__builtin_expect(both && sp >= kStackLds, 0)) {
-            overflow[(sp - kStackLds) * lanes + gl] = near_ref;
-            overflow[dist_half + (sp - kStackLds) * lanes + gl] = __float_as_uint(near_t);
+            overflow[(sp - kStackLds) * lanes + overflow_lane()] = near_ref;
+            overflow[dist_half + (sp - kStackLds) * lanes + overflow_lane()] = __float_as_uint(near_t);
         }
         if (both) sp++;
         ref = any ? next_ref : ref;
@@ -300,8 +311,8 @@ __global__ __launch_bounds__(kBlock) RT_TRACE_ATTR void trace_kernel(DevScene S,
             asm volatile("" : "+v"(e.x), "+v"(e.y));
             if (__builtin_expect(__ballot(sp >= kStackLds) != 0, 0)) {   // wave-uniform, rare
                 if (sp >= kStackLds) {
-                    e.x = overflow[(sp - kStackLds) * lanes + gl];
-                    e.y = overflow[dist_half + (sp - kStackLds) * lanes + gl];
+                    e.x = overflow[(sp - kStackLds) * lanes + overflow_lane()];
+                    e.y = overflow[dist_half + (sp - kStackLds) * lanes + overflow_lane()];
                 }
             }
             const bool take = !empty && !(__uint_as_float(e.y) >= closest);
@@ -316,6 +327,20 @@ __global__ __launch_bounds__(kBlock) RT_TRACE_ATTR void trace_kernel(DevScene S,
                 te = leaf ? ti + (int)((ref >> 24) & 0x3Fu) : te;
             }
             need = !empty && (!take || (leaf && ti == te));
+        }
+    };
+    // The result of slot s, whose ray this lane still holds: {closest, index}; VSLOT: the index, and the hit point
+    // for a lane that hit (contraction is off: the two roundings per component of shade_from's no = o + closest * d).
+    auto store_result = [&](int s) {
+        if (VSLOT) {
+            reinterpret_cast<int *>(hits)[s] = index;
+            if (index != -1) {
+                const V3 no = o + closest * d;
+                float *p = hit_org + (size_t)s * 3;
+                p[0] = no.x; p[1] = no.y; p[2] = no.z;
+            }
+        } else {
+            hits[s] = make_float2(closest, __int_as_float(index));
         }
     };
     // The root's child-pair record is the same for every ray: read once into scalar registers, so
@@ -350,7 +375,7 @@ __global__ __launch_bounds__(kBlock) RT_TRACE_ATTR void trace_kernel(DevScene S,
             // step's vmcnt(0) waits (before its record loads, before an LDS pop) wait for the write as
             // well; here the stores overlap the refill's own ray loads (A/B 7.13 -> 7.00 ms/pass)
             if (slot <= -2) {
-                hits[-2 - slot] = make_float2(closest, __int_as_float(index));
+                store_result(-2 - slot);
                 slot = -1;
             }
             bool fresh = false;
@@ -392,11 +417,11 @@ __global__ __launch_bounds__(kBlock) RT_TRACE_ATTR void trace_kernel(DevScene S,
                         o = S.cam;
                         d = primary_dir(S, (int)first_ray<FIRST>(pa.map, (uint32_t)slot), pa);
                     } else if (VSLOT) {
-                        // the slim bounce-0 hand-over (shade_kernel<.., SLIM>): 24-B records {o, d}
-                        const float2 *rp = reinterpret_cast<const float2 *>(geo) + (size_t)slot * 3;
-                        const float2 r0 = rp[0], r1 = rp[1], r2 = rp[2];
-                        o = v3(r0.x, r0.y, r1.x);
-                        d = v3(r1.y, r2.x, r2.y);
+                        // the slim bounce-0 hand-over (shade_kernel<.., SLIM>): 16-B records {d, t0}; the origin is
+                        // bounce 0's no = o + closest * d with o = cam and d = the slot's primary ray (shade_from)
+                        const float4 r = geo[slot];
+                        o = S.cam + r.w * primary_dir(S, slot, pa);
+                        d = v3(r.x, r.y, r.z);
                     } else {
                         const float4 *rp = geo + (size_t)slot * 2;   // ray state is in slot order
                         const float4 r0 = rp[0];
@@ -421,7 +446,7 @@ __global__ __launch_bounds__(kBlock) RT_TRACE_ATTR void trace_kernel(DevScene S,
                     if (ref & kLeaf) {
                         leaf_range(S, ref, ti, te);
                         if (ti == te) {  // no triangles at all: spheres only
-                            hits[slot] = make_float2(closest, __int_as_float(index));
+                            store_result(slot);
                             slot = -1;
                         }
                     }
@@ -497,7 +522,7 @@ __global__ __launch_bounds__(kBlock) RT_TRACE_ATTR void trace_kernel(DevScene S,
 #endif
         pop_loop(need);
     }
-    if (slot <= -2) hits[-2 - slot] = make_float2(closest, __int_as_float(index));
+    if (slot <= -2) store_result(-2 - slot);
     Counters *cs = ctr + ((blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) & (kCtrSlots - 1));
     const unsigned long long nl = wave_sum(nlive);
     if (COUNT) {
@@ -536,6 +561,7 @@ struct Shaded {
     bool acc_holds;                   // acc[ray] holds the radiance of the earlier bounces
     uint32_t mat;                     // SLIM only: the hit's material index and whether scatter multiplied T by its
     bool spec;                        // spec (else its diffuse) albedo
+    float t;                          // SLIM only: the hit's distance (no = cam + t * the primary direction)
 };
 constexpr uint32_t kSpecBit = 0x80;   // slim hand-over: Shaded::spec in a live bounce-0 bucket byte (buckets are 0..64)
 // INLINE (scenes without triangles): the closest hit is the sphere loop (scene.cu:338-372),
@@ -549,6 +575,7 @@ struct ShadeIn {
     bool acc_holds;                   // acc[ray] holds the ray's radiance so far (kAccFlag in its rid)
     float4 r0, r1;
     float tz;
+    const float *org;                 // shade_from<.., LEAN>: where a hit's point stands (3 floats); r0.xyz is unused
 };
 template <bool SORTED, int FIRST, bool INLINE>
 __device__ __forceinline__ ShadeIn shade_in(const PassArgs &pa, int slot, const float4 *__restrict__ geo,
@@ -575,10 +602,13 @@ __device__ __forceinline__ ShadeIn shade_in(const PassArgs &pa, int slot, const 
     return in;
 }
 // SLIM (bounce 0 of the virtual reorder's slim hand-over): also returns the hit's material index and albedo choice.
-template <bool SORTED, int FIRST, bool INLINE = false, bool SLIM = false>
+// LEAN (bounce 1 of it, shade_rank_kernel): the trace kernel wrote the hit point (trace_kernel<.., VSLOT>), read at
+// in.org by the lanes that hit, with the hit's other records; neither the ray's origin nor the hit's distance enters.
+template <bool SORTED, int FIRST, bool INLINE = false, bool SLIM = false, bool LEAN = false>
 __device__ __forceinline__ Shaded shade_from(const DevScene &S, const PassArgs &pa, int slot, const ShadeIn &in,
                                              uint32_t seed_term) {
     static_assert(!SLIM || FIRST == 1, "the slim hand-over leaves bounce 0, where T enters as (1,1,1)");
+    static_assert(!LEAN || (!FIRST && !INLINE), "the lean result is the bounce-1 trace kernel's");
     uint32_t mat = 0;
     bool spec = false;
     Rng rng = pcg_seed(in.seed * 4137874753u + seed_term);
@@ -625,8 +655,9 @@ __device__ __forceinline__ Shaded shade_from(const DevScene &S, const PassArgs &
         const bool sphere = index < S.sphere_count;
         const uint32_t mi = S.mat_idx[index];
         float4 q = *(sphere ? S.spheres + index : S.tris + (size_t)(index - S.sphere_count) * 3 + 2);
+        if (LEAN) no = v3(in.org[0], in.org[1], in.org[2]);   // the same round trip
         asm volatile("" : "+v"(q.x), "+v"(q.y), "+v"(q.z), "+v"(q.w));
-        no = o + closest * d;
+        if (!LEAN) no = o + closest * d;
         const V3 normal = sphere ? (1 / q.w) * (no - v3(q.x, q.y, q.z)) : v3(q.y, q.z, q.w);
         const float4 *mp = S.mats + (size_t)mi * 3;
         float4 m0 = mp[0], m1 = mp[1], m2 = mp[2];
@@ -639,7 +670,8 @@ __device__ __forceinline__ Shaded shade_from(const DevScene &S, const PassArgs &
             mat = mi;
         }
     }
-    return Shaded{no, nd, T, C, ray_id, index == -1 ? 0 : (index < S.sphere_count ? 2 : 1), in.acc_holds, mat, spec};
+    return Shaded{no, nd, T, C, ray_id, index == -1 ? 0 : (index < S.sphere_count ? 2 : 1), in.acc_holds, mat, spec,
+                  closest};
 }
 template <bool SORTED, int FIRST, bool INLINE = false, bool SLIM = false>
 __device__ __forceinline__ Shaded shade_one(const DevScene &S, const PassArgs &pa, int slot,
@@ -686,10 +718,11 @@ __device__ __forceinline__ unsigned long long match_bucket(uint32_t b, bool vali
 #else
 #define RT_SHADE_ATTR
 #endif
-// SLIM (bounce 0 of the virtual reorder, rt_renderer::vre): a surviving ray hands over 27 B instead of 41.  geo holds
-// 24-B records {o, d} (3 x float2 per slot), tz holds one u16 per slot, the hit's material index, and bit 7 of the
-// live bucket byte (kSpecBit) says which albedo scatter took; T and the rid flag are functions of those two
-// (shade_rank_kernel rebuilds them), so no T and no rid is written.
+// SLIM (bounce 0 of the virtual reorder, rt_renderer::vre): a surviving ray hands over 19 B instead of 41.  geo holds
+// one 16-B record {d, t0} per slot (t0: this bounce's hit distance; the new origin cam + t0 * primary_dir(slot) is
+// recomputed by the one kernel that needs it, the bounce-1 trace), tz holds one u16 per slot, the hit's material
+// index, and bit 7 of the live bucket byte (kSpecBit) says which albedo scatter took; T and the rid flag are functions
+// of those two (shade_rank_kernel rebuilds them), so no T and no rid is written.
 template <bool SORTED, bool COUNT, int FIRST, bool FUSED, bool INLINE, bool SLIM = false>
 __global__ __launch_bounds__(kBlock) RT_SHADE_ATTR void shade_kernel(DevScene S, PassArgs pa, float4 *__restrict__ geo,
                                                        float *__restrict__ tz, uint32_t *__restrict__ rid,
@@ -713,10 +746,7 @@ __global__ __launch_bounds__(kBlock) RT_SHADE_ATTR void shade_kernel(DevScene S,
         hit_sphere += sh.kind == 2;
         const bool dead = is_black(T);
         if (SLIM && !dead && !last) {
-            float2 *rec = reinterpret_cast<float2 *>(geo) + (size_t)slot * 3;
-            rec[0] = make_float2(no.x, no.y);
-            rec[1] = make_float2(no.z, nd.x);
-            rec[2] = make_float2(nd.y, nd.z);
+            geo[slot] = make_float4(nd.x, nd.y, nd.z, sh.t);
             reinterpret_cast<uint16_t *>(tz)[slot] = (uint16_t)sh.mat;
         }
         if (!SLIM && !FUSED && !dead && !last) {     // a terminated ray's geometry is never read again
@@ -1189,7 +1219,7 @@ __global__ __launch_bounds__(kBlock) RT_REPLAY_ATTR void sort_scatter_shade_kern
 // ---------------------------------------------------------------- virtual bounce-0 reorder
 // Sort on, untiled, a scene with triangles (rt_renderer::vre): the bounce-0 reorder moves nothing.  The reference's
 // sorted position matters to a ray only as the seed of its next shading, and only the rays alive at bounce 2 need
-// to stand in that order.  So bounce 0 shades once in place (shade_kernel<.., SLIM>, not FUSED: {o, d}, the hit's
+// to stand in that order.  So bounce 0 shades once in place (shade_kernel<.., SLIM>, not FUSED: {d, t0}, the hit's
 // material index, bucket + albedo bit, histogram, all in ray-id order) and sort_scan_kernel gives the bucket runs;
 // bounce 1 traces over the ray-id slots (trace_kernel<.., VSLOT>) and shade_rank_kernel computes each live slot's
 // sorted position with the scatter's own ranking, shades with that position as the seed, and moves only the survivors of bounce 1, to their
@@ -1209,8 +1239,10 @@ __global__ __launch_bounds__(kBlock) void fill_dead_kernel(uint8_t *__restrict__
 // Bounce 1 over the ray-id slots [0, *slot_count): the tiles and rounds of the bounce-0 histogram, the ranking of
 // sort_scatter_kernel on the bounce-0 buckets, shade_kernel's shading and radiance rules with seed = the sorted
 // position.  acc is indexed by ray id = slot, so a terminating ray's add is coalesced.
-// Input is the slim hand-over of shade_kernel<.., SLIM>: the 24-B record {o, d} at geo_in, the bounce-0 hit's
-// material index mat_in[slot] and kSpecBit of the bucket byte.  The rest of the state is rebuilt from the material:
+// Input is the slim hand-over of shade_kernel<.., SLIM>: the 16-B record {d, t0} at geo_in (d alone is read), the
+// bounce-0 hit's material index mat_in[slot] and kSpecBit of the bucket byte; and the lean result of
+// trace_kernel<.., VSLOT>: the hit index hit_idx[slot] and, read only by the lanes that hit, the hit point at
+// hit_org + 3 * slot (shade_from<.., LEAN>).  The rest of the state is rebuilt from the material:
 // T = 1 * (spec or diffuse albedo) is bounce 0's own multiply (scatter, T entering as the laundered (1,1,1)), and
 // rid = slot | kAccFlag iff has_radiance(0 + emit * 1), bounce 0's own term.  Survivors leave with the full state.
 template <bool COUNT>
@@ -1218,7 +1250,8 @@ __global__ __launch_bounds__(kBlock) RT_SHADE_ATTR void shade_rank_kernel(DevSce
                                                             const uint8_t *__restrict__ bkt_in,
                                                             const float4 *__restrict__ geo_in,
                                                             const uint16_t *__restrict__ mat_in,
-                                                            const float2 *__restrict__ hits, uint32_t seed_term, int last,
+                                                            const int *__restrict__ hit_idx,
+                                                            const float *__restrict__ hit_org, uint32_t seed_term, int last,
                                                             const uint32_t *__restrict__ slot_count, int tiles,
                                                             const uint32_t *__restrict__ offsets,
                                                             const uint32_t *__restrict__ totals,
@@ -1244,13 +1277,12 @@ __global__ __launch_bounds__(kBlock) RT_SHADE_ATTR void shade_rank_kernel(DevSce
             const uint32_t b = byte & ~kSpecBit;   // a dead slot is plain kDead
             const bool move = valid && b != kDead;
             ShadeIn in{};
-            float2 r0{}, r1{}, r2{};
+            float4 rec{};
             float4 alb{}, emi{};
             if (move) {                 // the loads overlap the ranking
                 const float4 *mp = S.mats + (size_t)mat_in[item] * 3;
-                in.h = hits[item];
-                const float2 *rp = reinterpret_cast<const float2 *>(geo_in) + (size_t)item * 3;
-                r0 = rp[0]; r1 = rp[1]; r2 = rp[2];
+                in.h = make_float2(0.f, __int_as_float(hit_idx[item]));
+                rec = geo_in[item];
                 alb = mp[byte & kSpecBit ? 1 : 0];   // {specular, rough} or {diffuse, metal}
                 emi = mp[2];
             }
@@ -1266,13 +1298,14 @@ __global__ __launch_bounds__(kBlock) RT_SHADE_ATTR void shade_rank_kernel(DevSce
                 asm volatile("" : "+v"(one));
                 const V3 ones = v3(one, one, one);
                 const V3 T0 = ones * v3(alb.x, alb.y, alb.z);
-                in.r0 = make_float4(r0.x, r0.y, r1.x, r1.y);
-                in.r1 = make_float4(r2.x, r2.y, T0.x, T0.y);
+                in.r0 = make_float4(0.f, 0.f, 0.f, rec.x);
+                in.r1 = make_float4(rec.y, rec.z, T0.x, T0.y);
                 in.tz = T0.z;
+                in.org = hit_org + (size_t)item * 3;
                 in.ray = (uint32_t)item;
                 in.acc_holds = has_radiance(v3(0, 0, 0) + v3(emi.x, emi.y, emi.z) * ones);
                 in.seed = pos;          // the reference's slot of this ray at bounce 1 (raytracing.cu:89)
-                const Shaded sh = shade_from<true, 0>(S, pa, item, in, seed_term);
+                const Shaded sh = shade_from<true, 0, false, false, true>(S, pa, item, in, seed_term);
                 const V3 no = sh.no, nd = sh.nd, T = sh.T;
                 miss += sh.kind == 0;
                 hit += sh.kind != 0;
@@ -1473,8 +1506,13 @@ struct PassCtx {
     // geo = 2 x float4 {o.xyz, d.x} {d.yz, T.xy}, tz = T.z, rid = the ray's acc index (+ kAccFlag): its ray id,
     // or its home index (Renderer::home).  acc[that] holds {T.z, C}: the radiance once a bounce added a nonzero
     // term, and finally when the ray terminates or after the last bounce.
-    // Renderer::vre, between bounce 0's shade and bounce 1's: geo[0] holds 24-B records {o, d} (3 x float2 per slot),
-    // tz[0] one u16 per slot (the bounce-0 hit's material index), rid[0] nothing (the slim hand-over, shade_kernel).
+    // Renderer::vre, between bounce 0's shade and bounce 1's (n = the pass's rays): geo[0] holds n 16-B records
+    // {d, t0} (one float4 per slot), tz[0] one u16 per slot (the bounce-0 hit's material index), rid[0] nothing (the
+    // slim hand-over, shade_kernel).  Bounce 1's trace result is lean: hits holds n 4-B hit indices (its first half),
+    // and geo[0]'s float4s [n, 1.75 n) hold 3 floats per slot, the hit point, written and read for hits only.
+    // Both are idle then: bounce 0's shade has read its hit records, nothing of geo[0] past the records is live until
+    // the reorder behind bounce 1 writes the buffer anew, and a slot's entries are written by the trace that
+    // shade_rank_kernel follows, so nothing of an earlier pass is read.
     DevBuf<float4> geo[2], acc;
     DevBuf<float> tz[2];
     DevBuf<uint32_t> rid[2], sort_counts, sort_offsets, sort_totals, live, queue, overflow;
@@ -1819,7 +1857,7 @@ struct rt_renderer {
         if (b == 0) RT_PROCESS3(SORTED, COUNT, 1); else RT_PROCESS3(SORTED, COUNT, 0);                           \
     } while (0)
             if (v0) {
-                // shades in place and hands over slim: 24-B records in geo[cur], material indices in tz[cur] (PassCtx)
+                // shades in place and hands over slim: 16-B records in geo[cur], material indices in tz[cur] (PassCtx)
 #define RT_V0PROCESS(COUNT)                                                                                      \
     do {                                                                                                         \
         hipLaunchKernelGGL((trace_kernel<true, COUNT, 1>), dim3(tgrid), dim3(kBlock), 0, st, scene.ds, pa,       \
@@ -1834,15 +1872,18 @@ struct rt_renderer {
 #undef RT_V0PROCESS
             } else if (v1) {
                 // every slot of the pass (live[0]); the state is still in ray-id order, the survivors' new state
-                // goes to their sorted positions of the other buffer set
+                // goes to their sorted positions of the other buffer set.  The trace's lean result: 4-B hit indices in
+                // hits, the hit points behind the n 16-B records of geo[cur] (12 n of its free 16 n bytes; PassCtx)
+                float *hit_org = reinterpret_cast<float *>(c.geo[cur].p + n);
 #define RT_VPROCESS(COUNT)                                                                                       \
     do {                                                                                                         \
         hipLaunchKernelGGL((trace_kernel<true, COUNT, 0, true>), dim3(tgrid), dim3(kBlock), 0, st, scene.ds, pa, \
                            c.geo[cur].p, c.live.p, q, c.hits.p, c.overflow.p, scene.ctr.p,                       \
-                           tspan ? tspan + kSpanWords * b : nullptr, c.bkt.p);                                   \
+                           tspan ? tspan + kSpanWords * b : nullptr, c.bkt.p, hit_org);                          \
         if (em) HIPCHK(hipEventRecord(em, st));                                                                  \
         hipLaunchKernelGGL((shade_rank_kernel<COUNT>), dim3(sort_grid), dim3(kBlock), 0, st, scene.ds, pa, c.bkt.p, \
-                           c.geo[cur].p, reinterpret_cast<const uint16_t *>(c.tz[cur].p), c.hits.p, seed_term,   \
+                           c.geo[cur].p, reinterpret_cast<const uint16_t *>(c.tz[cur].p),                        \
+                           reinterpret_cast<const int *>(c.hits.p), hit_org, seed_term,                          \
                            (int)last, c.live.p, tiles, c.sort_offsets.p, c.sort_totals.p, c.geo[1 - cur].p,      \
                            c.tz[1 - cur].p, c.rid[1 - cur].p, c.bkt1.p, c.acc.p, scene.ctr.p);                   \
     } while (0)
