@@ -104,6 +104,11 @@ __device__ __forceinline__ int fkey(float f) {
 }
 __device__ __forceinline__ float funkey(int k) { return __int_as_float(k >= 0 ? k : k ^ 0x7fffffff); }
 
+// min(BINS - 1, (int)p) wherever that is defined; a NaN p (0 * an infinite scale, from a denormal centroid
+// range) goes to bin 0 and an infinite p to the last bin, spelled out so that nothing rests on what an
+// out-of-range float-to-int conversion yields.  The host build and the oracle do the same.
+__device__ __forceinline__ int bin_of(float p) { return p >= (float)kBins ? kBins - 1 : (p > 0.0f ? (int)p : 0); }
+
 __device__ __forceinline__ float half_area(const float lo[3], const float hi[3]) {   // scene.cu:853-858
     const float x = hi[0] - lo[0], y = hi[1] - lo[1], z = hi[2] - lo[2];
     return x * y + x * z + y * z;
@@ -247,7 +252,7 @@ __global__ __launch_bounds__(kThreads) void bounds_kernel(const NodeRange *__res
             const int kl[3] = {fkey(l.x), fkey(l.y), fkey(l.z)}, kh[3] = {fkey(h.x), fkey(h.y), fkey(h.z)};
             for (int a = 0; a < 3; a++) {
                 if (cmin[a] == cmax[a]) continue;
-                const int b = min(kBins - 1, (int)((cc[a] - cmin[a]) * scale[a]));   // scene.cu:918
+                const int b = bin_of((cc[a] - cmin[a]) * scale[a]);                  // scene.cu:918
                 if (kWaves == 1) {      // one-wave nodes (<= 4096 triangles): plain per-lane atomics
                     if (valid) {
                         atomicAdd(&s_wcnt[w][a][b], 1);

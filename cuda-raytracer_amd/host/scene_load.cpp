@@ -110,6 +110,12 @@ private:
     std::vector<float> cent_[3];
     std::atomic<int> spare_threads_{0};
 
+    // std::min(BINS - 1, (int)p) of scene.cu:916 wherever that is defined (0 <= p < 2^31).  A centroid
+    // range below 8 / FLT_MAX (denormal) makes the scale infinite: p is then NaN at min_centroid and inf
+    // above it, whose conversion is undefined (an out-of-bounds bin on x86).  Here, in the oracle and on
+    // the device the conversion saturates: NaN to bin 0, inf to the last bin.
+    static int bin_of(float p) { return p >= (float)kBins ? kBins - 1 : (p > 0.0f ? (int)p : 0); }
+
     static rt_bvh_node fresh(int lo, int hi) {  // a child as the reference creates it
         rt_bvh_node n{};
         n.min_bound = {1e30f, 1e30f, 1e30f};
@@ -151,7 +157,7 @@ private:
             Box bins[kBins];
             int counts[kBins] = {0};
             for (int i = lo; i < hi; i++) {
-                const int b = std::min(kBins - 1, (int)((c[i] - cmin) * k));
+                const int b = bin_of((c[i] - cmin) * k);
                 counts[b]++;
                 bins[b].grow(box_[i]);
             }
@@ -483,6 +489,22 @@ int rt_scene_load(const char *path, const rt_load_opts *opts_in, rt_scene_host *
         return bad(fail(RT_E_INVALID, "scene too large"));
     s->material_indices = sphere_mats;
     s->material_indices.insert(s->material_indices.end(), tri_mats.begin(), tri_mats.end());
+    // Both BVH builders bin by (int)((centroid - min_centroid) * scale) (scene.cu:916): with a NaN or
+    // infinite coordinate, or vertices whose sum overflows, that product is NaN, and its conversion is
+    // undefined behaviour in the reference (an out-of-bounds bin on x86).  Such a scene has no answer to
+    // agree with, so it is refused here, before either builder runs.
+    auto finite3 = [](rt_vec3 p) { return std::isfinite(p.x) && std::isfinite(p.y) && std::isfinite(p.z); };
+    for (size_t i = 0; i < s->spheres.size(); i++)
+        if (!finite3(s->spheres[i].center) || !std::isfinite(s->spheres[i].radius))
+            return bad(fail(RT_E_INVALID, "sphere " + std::to_string(i) + " has a non-finite coordinate or radius"));
+    for (size_t i = 0; i < s->triangles.size(); i++) {
+        const rt_triangle &tr = s->triangles[i];
+        if (!finite3(tr.p1) || !finite3(tr.p2p1) || !finite3(tr.p3p1))
+            return bad(fail(RT_E_INVALID, "triangle " + std::to_string(i) + " has a non-finite coordinate"));
+        if (!finite3(tr.normal))
+            return bad(fail(RT_E_INVALID, "triangle " + std::to_string(i) + " has a non-finite centroid: the sum "
+                                          "of its vertices overflows"));
+    }
 
     // Camera precompute (scene.cu:62-76).
     const rt_vec3 right = cross(v.up, v.forward);

@@ -90,6 +90,9 @@ typedef struct {
 
 typedef struct rt_scene_host rt_scene_host;   /* owns the arrays a rt_scene points into */
 
+/* Refuses (RT_E_INVALID, the message names the primitive; before either BVH builder runs) a triangle or
+ * sphere with a NaN or infinite coordinate or radius, and a triangle whose vertex sum overflows (a
+ * non-finite centroid): the reference's bin index (scene.cu:916) is undefined for them. */
 int rt_scene_load(const char *path, const rt_load_opts *opts, rt_scene_host **out);
 const rt_scene *rt_scene_view(const rt_scene_host *scene);
 double rt_scene_bvh_ms(const rt_scene_host *scene);          /* "BVH Took" (scene.cu:1026) */

@@ -233,7 +233,10 @@ void maybe_split(orc_scene *s, int node_index, int max_depth) {
         Aabb bin_box[BINS];
         int bin_count[BINS] = {0};
         for (int i = c2; i < c1; i++) {
-            const int b = std::min(BINS - 1, (int)((comp(tris[i].normal, axis) - min_c) * scale));
+            // std::min(BINS - 1, (int)p) wherever that is defined; NaN -> 0 and inf -> BINS - 1 (an infinite
+            // scale, from a denormal centroid range) instead of undefined behaviour
+            const float p = (comp(tris[i].normal, axis) - min_c) * scale;
+            const int b = p >= (float)BINS ? BINS - 1 : (p > 0.0f ? (int)p : 0);
             bin_count[b]++;
             bin_box[b].expand(tris[i]);
         }

@@ -76,3 +76,23 @@ def test_loader_errors(tmp_path):
     p.write_text("material m\nply m nowhere.ply\n")
     with pytest.raises(R.RtError, match="cannot open ply"):
         R.Scene(str(p))
+    # Non-finite geometry: the bin index (int)((centroid - min_centroid) * scale) of scene.cu:916 is undefined
+    # for a NaN product (the host build used to crash on these files).  Refused for both builders.
+    six = ["0 0 0 1 0 0 0 1 0", "2 0 0 3 0 0 2 1 0", "4 0 1 5 0 0 4 1 0", "6 0 0 %s 0 2 6 1 0", "8 1 0 9 0 0 8 1 3",
+           "10 0 0 11 0 0 10 1 0"]
+    text = "material m\n" + "".join("triangle m %s\n" % t for t in six)
+    for bad, what in (("nan", "triangle 3 has a non-finite coordinate"), ("inf", "triangle 3 has a non-finite coordinate"),
+                      ("-inf", "triangle 3 has a non-finite coordinate"),
+                      ("3e38 0 0 3e38", "triangle 3 has a non-finite centroid")):     # p2.x + p3.x overflows
+        p.write_text(text % bad)
+        for use_bvh in (True, False):
+            with pytest.raises(R.RtError, match=what):
+                R.Scene(str(p), use_bvh=use_bvh)
+    p.write_text("material m\nsphere m 0 nan 0 1\n")
+    with pytest.raises(R.RtError, match="sphere 0 has a non-finite"):
+        R.Scene(str(p))
+    p.write_text("material m\nsphere m 0 0 0 inf\n")
+    with pytest.raises(R.RtError, match="sphere 0 has a non-finite"):
+        R.Scene(str(p))
+    p.write_text(text % "3e38")                  # one huge coordinate is finite, and so is the centroid: it loads
+    assert R.Scene(str(p)).view.bvh_node_count == 1
