@@ -184,6 +184,23 @@ __device__ __forceinline__ V3 primary_dir(const DevScene &S, int i, const PassAr
 #ifndef RT_SORT_GRID
 #define RT_SORT_GRID 0                // cap on the reorder's hist/scatter grid (0: 8 blocks per CU)
 #endif
+// The reorder kernels walk their tiles on at most 8 workgroups per CU.  The test build (librtamd_test.so) reads
+// another cap from RTAMD_TEST_SORT_GRID, so that a small render gives every workgroup several tiles.
+inline int reorder_grid_cap(int cus) {
+#ifdef RTAMD_TEST_HOOKS
+    if (const char *e = std::getenv("RTAMD_TEST_SORT_GRID"))
+        if (std::atoi(e) > 0) return std::atoi(e);
+#endif
+    return cus * 8;
+}
+// The shade kernel walks the same tiles where it counts the buckets (shade_kernel's `counts`), so under the test
+// cap its grid is capped alike; without it, RT_SHADE_BPC workgroups per CU.
+inline int shade_grid_cap(int cus, int bpc) {
+#ifdef RTAMD_TEST_HOOKS
+    if (reorder_grid_cap(cus) != cus * 8) return reorder_grid_cap(cus);
+#endif
+    return cus * bpc;
+}
 
 // Closest hit for the live slots [0, *live): the sphere loop (scene.cu:338-372) and
 // bvh_closest_hit_distance (scene.cu:134-241).  Persistent and wave-refilling: each wave takes
@@ -1791,10 +1808,10 @@ struct rt_renderer {
         const int grid = blocks_for(n);
         const int tiles = tile_stride(n);     // counts stride; a launch's tiles follow its live count
         const int tgrid = std::min(grid, trace_blocks);
-        const int sgrid = std::min(grid, scene.cus * RT_SHADE_BPC);
+        const int sgrid = std::min(grid, shade_grid_cap(scene.cus, RT_SHADE_BPC));
         // tile-stride reorder kernels on at most 8 blocks per CU: in the tail bounces a block per
         // possible tile dispatched ~10^4 empty workgroups per launch (A/B: +0.3-0.5 %)
-        const int sort_grid = std::max(1, std::min(max_tiles(n), RT_SORT_GRID > 0 ? RT_SORT_GRID : scene.cus * 8));
+        const int sort_grid = std::max(1, std::min(max_tiles(n), RT_SORT_GRID > 0 ? RT_SORT_GRID : reorder_grid_cap(scene.cus)));
         hipStream_t st = c.stream;
         int cur = 0;
         if (n == 0) {                           // a tile owner with no stripe of this image
@@ -2093,7 +2110,7 @@ struct rt_renderer {
             if (rc) return rtamd::fail(RT_E_INVALID, "tile exchange callback failed (" + std::to_string(rc) + ")");
         }
         const int tg = c.t_tiles_g;
-        const int ggrid = std::max(1, std::min(max_tiles((int64_t)lg), scene.cus * 8));
+        const int ggrid = std::max(1, std::min(max_tiles((int64_t)lg), reorder_grid_cap(scene.cus)));
         // global: buckets of every live slot -> new global slots of this owner's slots (newpos) and
         // the next global live count
         hipLaunchKernelGGL(gsort_hist_kernel, dim3(ggrid), dim3(kBlock), 0, st, c.gbytes.p, c.glive.p, tg,
@@ -2109,7 +2126,7 @@ struct rt_renderer {
         // each carrying its new global slot
         const uint32_t *lv = c.live.p + b;
         const int tiles = tile_stride(c.t_n);
-        const int sort_grid = std::max(1, std::min(max_tiles(c.t_n), RT_SORT_GRID > 0 ? RT_SORT_GRID : scene.cus * 8));
+        const int sort_grid = std::max(1, std::min(max_tiles(c.t_n), RT_SORT_GRID > 0 ? RT_SORT_GRID : reorder_grid_cap(scene.cus)));
         const int cur = c.t_cur;
         hipLaunchKernelGGL(sort_hist_kernel, dim3(sort_grid), dim3(kBlock), 0, st, c.bkt.p, lv, tiles, c.sort_counts.p);
         hipLaunchKernelGGL(sort_scan_kernel, dim3(kBuckets), dim3(kBlock), 0, st, c.sort_counts.p, lv, tiles,
@@ -2831,3 +2848,271 @@ int rt_bloom(float *fb, int32_t w, int32_t h, float threshold, int32_t radius, i
 }
 
 }  // extern "C"
+
+#ifdef RTAMD_TEST_HOOKS
+// ---- Test build only (librtamd_test.so, -DRTAMD_TEST_HOOKS; the product library has none of this).
+// Direct entry points to the reorder kernels for tests/test_gpu_reorder.py: each takes host arrays, launches the
+// kernels above, unchanged, with the renderer's own stride (tile_stride(capacity)) and grid (max_tiles(n) under
+// reorder_grid_cap, or the caller's grid), on one stream, and copies the results back.  Arrays the kernels write
+// are in/out: the caller's words (a sentinel, with guard words behind the payload) go to the device first, so
+// what comes back shows every store.  Indices a kernel would store through are checked on the host first.
+namespace {
+
+struct TestDev {
+    int cus = 0;
+    hipStream_t st = nullptr;
+    ~TestDev() { if (st) (void)hipStreamDestroy(st); }
+    int init(int device) {
+        if (device < 0 || device >= rt_device_count()) return rtamd::fail(RT_E_NODEVICE, "no such HIP device");
+        HIPCHK(hipSetDevice(device));
+        HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+        HIPCHK(hipStreamCreate(&st));
+        return RT_OK;
+    }
+    int grid(int64_t n, int override_grid) const {
+        return override_grid > 0 ? override_grid
+                                 : std::max(1, std::min(max_tiles(n), RT_SORT_GRID > 0 ? RT_SORT_GRID : reorder_grid_cap(cus)));
+    }
+};
+
+template <class T>
+int test_upload(DevBuf<T> &b, const T *src, size_t count, hipStream_t st) {
+    if (int rc = b.alloc(std::max<size_t>(count, 1))) return rc;   // never a null kernel argument
+    if (count) HIPCHK(hipMemcpyAsync(b.p, src, count * sizeof(T), hipMemcpyHostToDevice, st));
+    return RT_OK;
+}
+template <class T>
+int test_download(T *dst, const DevBuf<T> &b, size_t count, hipStream_t st) {
+    if (count) HIPCHK(hipMemcpyAsync(dst, b.p, count * sizeof(T), hipMemcpyDeviceToHost, st));
+    return RT_OK;
+}
+int test_fill(DevBuf<uint32_t> &b, size_t count, uint32_t word, hipStream_t st) {
+    if (int rc = b.alloc(std::max<size_t>(count, 1))) return rc;
+    if (count) HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(b.p), (int)word, count, st));
+    return RT_OK;
+}
+bool buckets_ok(const uint8_t *b, int n) {
+    for (int i = 0; i < n; i++)
+        if (b[i] > kDead) return false;
+    return true;
+}
+// SlotMap::ray on the host, in plain division
+uint64_t host_slot_ray(uint32_t s, uint32_t stripe, int count, int index) {
+    return (uint64_t)s + (uint64_t)(s / stripe) * (uint32_t)(count - 1) * stripe + (uint64_t)index * stripe;
+}
+bool slot_map_ok(uint32_t stripe, int count, int index, int n_local, int n_global) {
+    if (stripe == 0 || count < 1 || index < 0 || index >= count) return false;
+    return n_local == 0 || host_slot_ray((uint32_t)n_local - 1, stripe, count, index) < (uint64_t)n_global;
+}
+bool slots_ok(const uint32_t *gslot, int n_local, int n_global) {
+    for (int i = 0; i < n_local; i++)
+        if (gslot[i] >= (uint32_t)n_global) return false;
+    return true;
+}
+
+// the scratch of one hist -> scan -> rank/scatter chain, pre-filled with `fill`
+struct TestScratch {
+    DevBuf<uint32_t> counts, offsets, totals, live;   // live: {n, live_next, bad}
+    int stride = 0;
+    int init(int n, int64_t capacity, uint32_t fill, hipStream_t st) {
+        stride = tile_stride(capacity);
+        int rc;
+        if ((rc = test_fill(counts, (size_t)kBuckets * stride, fill, st))) return rc;
+        if ((rc = test_fill(offsets, (size_t)kBuckets * stride, fill, st))) return rc;
+        if ((rc = test_fill(totals, kBuckets, fill, st))) return rc;
+        if ((rc = test_fill(live, 3, fill, st))) return rc;
+        const uint32_t head[3] = {(uint32_t)n, fill, 0u};
+        HIPCHK(hipMemcpyAsync(live.p, head, sizeof(head), hipMemcpyHostToDevice, st));
+        HIPCHK(hipStreamSynchronize(st));       // head is a local
+        return RT_OK;
+    }
+    int read(uint32_t *c, uint32_t *o, uint32_t *t, hipStream_t st) const {
+        int rc;
+        if (c && (rc = test_download(c, counts, (size_t)kBuckets * stride, st))) return rc;
+        if (o && (rc = test_download(o, offsets, (size_t)kBuckets * stride, st))) return rc;
+        if (t && (rc = test_download(t, totals, kBuckets, st))) return rc;
+        return RT_OK;
+    }
+};
+
+__global__ __launch_bounds__(kBlock) void fastdiv_test_kernel(const FastDiv *__restrict__ f, const uint32_t *__restrict__ n,
+                                                              int count, uint32_t *__restrict__ out) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i < count) out[i] = f[i].div(n[i]);
+}
+
+}  // namespace
+
+extern "C" {
+
+// sort_hist_kernel -> sort_scan_kernel -> sort_scatter_kernel<0> over n slots of buckets bkt[] (0..64).
+// geo_in (8 words per slot), tz_in, rid_in: the payload.  geo_out, tz_out, rid_out: in/out, out_slots slots each.
+// counts, offsets (65 * stride words), totals (65), live_next (1): out.  stride = tile_stride(capacity) must be
+// the caller's; *grid_out = the grid launched.
+int rtamd_test_reorder_plain(int device, const uint8_t *bkt, int n, int64_t capacity, int grid, uint32_t fill, int stride,
+                             const uint32_t *geo_in, const uint32_t *tz_in, const uint32_t *rid_in, uint32_t *geo_out,
+                             uint32_t *tz_out, uint32_t *rid_out, int64_t out_slots, uint32_t *counts, uint32_t *offsets,
+                             uint32_t *totals, uint32_t *live_next, int *grid_out) {
+    if (n < 0 || capacity < n || out_slots < n || !buckets_ok(bkt, n))
+        return rtamd::fail(RT_E_INVALID, "rtamd_test_reorder_plain: bad argument");
+    if (stride != tile_stride(capacity)) return rtamd::fail(RT_E_INVALID, "rtamd_test_reorder_plain: stride is not tile_stride(capacity)");
+    TestDev d;
+    TestScratch s;
+    int rc;
+    if ((rc = d.init(device)) || (rc = s.init(n, capacity, fill, d.st))) return rc;
+    DevBuf<uint8_t> b;
+    DevBuf<uint32_t> gi, ti, ri, go, to, ro;
+    if ((rc = test_upload(b, bkt, (size_t)n, d.st)) || (rc = test_upload(gi, geo_in, (size_t)n * 8, d.st)) ||
+        (rc = test_upload(ti, tz_in, (size_t)n, d.st)) || (rc = test_upload(ri, rid_in, (size_t)n, d.st)) ||
+        (rc = test_upload(go, geo_out, (size_t)out_slots * 8, d.st)) || (rc = test_upload(to, tz_out, (size_t)out_slots, d.st)) ||
+        (rc = test_upload(ro, rid_out, (size_t)out_slots, d.st)))
+        return rc;
+    const int g = d.grid(n, grid);
+    hipLaunchKernelGGL(sort_hist_kernel, dim3(g), dim3(kBlock), 0, d.st, b.p, s.live.p, s.stride, s.counts.p);
+    hipLaunchKernelGGL(sort_scan_kernel, dim3(kBuckets), dim3(kBlock), 0, d.st, s.counts.p, s.live.p, s.stride, s.offsets.p,
+                       s.totals.p, s.live.p + 1);
+    hipLaunchKernelGGL(sort_scatter_kernel<0>, dim3(g), dim3(kBlock), 0, d.st, b.p, reinterpret_cast<const float4 *>(gi.p),
+                       reinterpret_cast<const float *>(ti.p), ri.p, s.live.p, s.stride, s.offsets.p, s.totals.p,
+                       reinterpret_cast<float4 *>(go.p), reinterpret_cast<float *>(to.p), ro.p, SlotMap::identity());
+    HIPCHK(hipGetLastError());
+    if ((rc = s.read(counts, offsets, totals, d.st)) || (rc = test_download(geo_out, go, (size_t)out_slots * 8, d.st)) ||
+        (rc = test_download(tz_out, to, (size_t)out_slots, d.st)) || (rc = test_download(rid_out, ro, (size_t)out_slots, d.st)))
+        return rc;
+    HIPCHK(hipMemcpyAsync(live_next, s.live.p + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, d.st));
+    HIPCHK(hipStreamSynchronize(d.st));
+    if (grid_out) *grid_out = g;
+    return RT_OK;
+}
+
+// Pixel tiles with the reorder on.  Stage 1: gsort_hist_kernel -> sort_scan_kernel -> sort_rank_kernel over the
+// exchanged bytes g[] (any value) and this owner's bytes own[], n_global each.  newpos: in/out, newpos_slots words.
+// bad, live_next (1 word each), counts, offsets, totals: out, as above.
+// Stage 2 (n_local >= 0): this owner's n_local rays, buckets bkt_local[], reordered as tsort_back does it --
+// sort_hist_kernel -> sort_scan_kernel -> sort_scatter_kernel<form> with stage 1's newpos; form 0 reads the old
+// global slots from gslot_in[], form 2 takes them from SlotMap::of(stripe, tile_count, tile_index).  gslot_out:
+// in/out, gslot_out_slots words; live_next_local: out.
+int rtamd_test_reorder_global(int device, const uint8_t *g, const uint8_t *own, int n_global, int64_t capacity, int grid,
+                              uint32_t fill, int stride, uint32_t *newpos, int64_t newpos_slots, uint32_t *bad,
+                              uint32_t *live_next, uint32_t *counts, uint32_t *offsets, uint32_t *totals, int *grid_out,
+                              int n_local, const uint8_t *bkt_local, const uint32_t *gslot_in, int form, uint32_t stripe,
+                              int tile_count, int tile_index, uint32_t *gslot_out, int64_t gslot_out_slots,
+                              uint32_t *live_next_local) {
+    if (n_global < 0 || capacity < n_global || newpos_slots < n_global)
+        return rtamd::fail(RT_E_INVALID, "rtamd_test_reorder_global: bad argument");
+    if (stride != tile_stride(capacity)) return rtamd::fail(RT_E_INVALID, "rtamd_test_reorder_global: stride is not tile_stride(capacity)");
+    if (n_local >= 0) {
+        const bool ok = n_local <= n_global && gslot_out_slots >= n_local && buckets_ok(bkt_local, n_local) &&
+                        (form == 0 ? slots_ok(gslot_in, n_local, n_global)
+                                   : form == 2 && slot_map_ok(stripe, tile_count, tile_index, n_local, n_global));
+        if (!ok) return rtamd::fail(RT_E_INVALID, "rtamd_test_reorder_global: bad local stage");
+    }
+    TestDev d;
+    TestScratch s;
+    int rc;
+    if ((rc = d.init(device)) || (rc = s.init(n_global, capacity, fill, d.st))) return rc;
+    DevBuf<uint8_t> gb, ob;
+    DevBuf<uint32_t> np;
+    if ((rc = test_upload(gb, g, (size_t)n_global, d.st)) || (rc = test_upload(ob, own, (size_t)n_global, d.st)) ||
+        (rc = test_upload(np, newpos, (size_t)newpos_slots, d.st)))
+        return rc;
+    const int gg = d.grid(n_global, grid);
+    hipLaunchKernelGGL(gsort_hist_kernel, dim3(gg), dim3(kBlock), 0, d.st, gb.p, s.live.p, s.stride, s.counts.p, s.live.p + 2);
+    hipLaunchKernelGGL(sort_scan_kernel, dim3(kBuckets), dim3(kBlock), 0, d.st, s.counts.p, s.live.p, s.stride, s.offsets.p,
+                       s.totals.p, s.live.p + 1);
+    hipLaunchKernelGGL(sort_rank_kernel, dim3(gg), dim3(kBlock), 0, d.st, gb.p, ob.p, s.live.p, s.stride, s.offsets.p,
+                       s.totals.p, np.p);
+    HIPCHK(hipGetLastError());
+    if ((rc = s.read(counts, offsets, totals, d.st)) || (rc = test_download(newpos, np, (size_t)newpos_slots, d.st))) return rc;
+    HIPCHK(hipMemcpyAsync(live_next, s.live.p + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, d.st));
+    HIPCHK(hipMemcpyAsync(bad, s.live.p + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, d.st));
+    HIPCHK(hipStreamSynchronize(d.st));
+    if (grid_out) *grid_out = gg;
+    if (n_local < 0) return RT_OK;
+
+    TestScratch l;
+    if ((rc = l.init(n_local, n_local, fill, d.st))) return rc;
+    DevBuf<uint8_t> lb;
+    DevBuf<uint32_t> gin, gout, go, to, ro, gi, ti, ri;
+    const size_t nl = (size_t)n_local;
+    if ((rc = test_upload(lb, bkt_local, nl, d.st)) || (rc = test_upload(gout, gslot_out, (size_t)gslot_out_slots, d.st)) ||
+        (rc = test_fill(gi, nl * 8, 0u, d.st)) || (rc = test_fill(ti, nl, 0u, d.st)) || (rc = test_fill(ri, nl, 0u, d.st)) ||
+        (rc = test_fill(go, nl * 8, 0u, d.st)) || (rc = test_fill(to, nl, 0u, d.st)) || (rc = test_fill(ro, nl, 0u, d.st)))
+        return rc;
+    if (form == 0) { if ((rc = test_upload(gin, gslot_in, nl, d.st))) return rc; }
+    else if ((rc = test_fill(gin, nl, fill, d.st))) return rc;
+    const int lg = d.grid(n_local, grid);
+    const SlotMap map = form == 2 ? SlotMap::of(stripe, tile_count, tile_index) : SlotMap::identity();
+    hipLaunchKernelGGL(sort_hist_kernel, dim3(lg), dim3(kBlock), 0, d.st, lb.p, l.live.p, l.stride, l.counts.p);
+    hipLaunchKernelGGL(sort_scan_kernel, dim3(kBuckets), dim3(kBlock), 0, d.st, l.counts.p, l.live.p, l.stride, l.offsets.p,
+                       l.totals.p, l.live.p + 1);
+#define RT_TEST_SCATTER(FORM)                                                                                          \
+    hipLaunchKernelGGL(sort_scatter_kernel<FORM>, dim3(lg), dim3(kBlock), 0, d.st, lb.p, reinterpret_cast<const float4 *>(gi.p), \
+                       reinterpret_cast<const float *>(ti.p), ri.p, l.live.p, l.stride, l.offsets.p, l.totals.p,       \
+                       reinterpret_cast<float4 *>(go.p), reinterpret_cast<float *>(to.p), ro.p, map, gin.p, np.p, gout.p)
+    if (form == 2) RT_TEST_SCATTER(2); else RT_TEST_SCATTER(0);
+#undef RT_TEST_SCATTER
+    HIPCHK(hipGetLastError());
+    if ((rc = test_download(gslot_out, gout, (size_t)gslot_out_slots, d.st))) return rc;
+    HIPCHK(hipMemcpyAsync(live_next_local, l.live.p + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, d.st));
+    HIPCHK(hipStreamSynchronize(d.st));
+    return RT_OK;
+}
+
+// zero_bytes_kernel over n_global bytes of G and L (in/out, `slots` bytes each), then tile_bytes_kernel<0> (gslot
+// given) or <1> (gslot null: SlotMap::of(stripe, tile_count, tile_index)) for n_local rays of buckets bkt[]; the
+// renderer's grids (tsort_front).
+int rtamd_test_tile_bytes(int device, const uint8_t *bkt, int n_local, const uint32_t *gslot, uint32_t stripe,
+                          int tile_count, int tile_index, int n_global, uint8_t *G, uint8_t *L, int64_t slots) {
+    const bool ok = n_local >= 0 && n_global >= 0 && n_local <= n_global && slots >= n_global && buckets_ok(bkt, n_local) &&
+                    (gslot ? slots_ok(gslot, n_local, n_global) : slot_map_ok(stripe, tile_count, tile_index, n_local, n_global));
+    if (!ok) return rtamd::fail(RT_E_INVALID, "rtamd_test_tile_bytes: bad argument");
+    TestDev d;
+    int rc;
+    if ((rc = d.init(device))) return rc;
+    DevBuf<uint8_t> b, gb, lb;
+    DevBuf<uint32_t> gs, cnt;
+    const uint32_t head[2] = {(uint32_t)n_global, (uint32_t)n_local};
+    if ((rc = test_upload(b, bkt, (size_t)n_local, d.st)) || (rc = test_upload(gb, G, (size_t)slots, d.st)) ||
+        (rc = test_upload(lb, L, (size_t)slots, d.st)) || (rc = test_upload(gs, gslot, gslot ? (size_t)n_local : 0, d.st)) ||
+        (rc = test_upload(cnt, head, 2, d.st)))
+        return rc;
+    const int zgrid = std::max(1, std::min(blocks_for((int64_t)((uint64_t)n_global + 15) / 16), d.cus * 8));
+    const int sgrid = std::max(1, std::min(blocks_for(n_local), d.cus * RT_SHADE_BPC));
+    hipLaunchKernelGGL(zero_bytes_kernel, dim3(zgrid), dim3(kBlock), 0, d.st, gb.p, lb.p, cnt.p);
+    if (gslot)
+        hipLaunchKernelGGL(tile_bytes_kernel<0>, dim3(sgrid), dim3(kBlock), 0, d.st, b.p, cnt.p + 1, gs.p, SlotMap::identity(),
+                           gb.p, lb.p);
+    else
+        hipLaunchKernelGGL(tile_bytes_kernel<1>, dim3(sgrid), dim3(kBlock), 0, d.st, b.p, cnt.p + 1, gs.p,
+                           SlotMap::of(stripe, tile_count, tile_index), gb.p, lb.p);
+    HIPCHK(hipGetLastError());
+    if ((rc = test_download(G, gb, (size_t)slots, d.st)) || (rc = test_download(L, lb, (size_t)slots, d.st))) return rc;
+    HIPCHK(hipStreamSynchronize(d.st));
+    return RT_OK;
+}
+
+// out[i] = FastDiv::of(d[i]).div(n[i]) on the device (d[i] >= 1, n[i] < 2^31)
+int rtamd_test_fastdiv(int device, const uint32_t *dv, const uint32_t *nv, int count, uint32_t *out) {
+    if (count < 0 || !dv || !nv || !out) return rtamd::fail(RT_E_INVALID, "rtamd_test_fastdiv: bad argument");
+    std::vector<FastDiv> f((size_t)count);
+    for (int i = 0; i < count; i++) {
+        if (dv[i] == 0 || nv[i] >= 0x80000000u) return rtamd::fail(RT_E_INVALID, "rtamd_test_fastdiv: d = 0 or n >= 2^31");
+        f[(size_t)i] = FastDiv::of(dv[i]);
+    }
+    TestDev d;
+    int rc;
+    if ((rc = d.init(device))) return rc;
+    DevBuf<FastDiv> fb;
+    DevBuf<uint32_t> nb, ob;
+    if ((rc = test_upload(fb, f.data(), (size_t)count, d.st)) || (rc = test_upload(nb, nv, (size_t)count, d.st)) ||
+        (rc = test_fill(ob, (size_t)count, 0xFFFFFFFFu, d.st)))
+        return rc;
+    hipLaunchKernelGGL(fastdiv_test_kernel, dim3(std::max(1, blocks_for(count))), dim3(kBlock), 0, d.st, fb.p, nb.p, count, ob.p);
+    HIPCHK(hipGetLastError());
+    if ((rc = test_download(out, ob, (size_t)count, d.st))) return rc;
+    HIPCHK(hipStreamSynchronize(d.st));
+    return RT_OK;
+}
+
+}  // extern "C"
+#endif  // RTAMD_TEST_HOOKS

@@ -364,7 +364,8 @@ def lib():
 
 
 def test_lib():
-    """librtamd_test.so (the test-hook build: RTAMD_MULTI_LOOPBACK, RTAMD_FAIL_AFTER_SETUP), for tests.
+    """librtamd_test.so (the test-hook build: RTAMD_MULTI_LOOPBACK, RTAMD_FAIL_AFTER_SETUP, RTAMD_TEST_SORT_GRID and
+    the rtamd_test_* entry points to the reorder kernels), for tests.
     Scenes loaded through lib() can be passed to it: rt_scene is a plain host view."""
     global _test_lib
     if _test_lib is None:
@@ -1324,44 +1325,49 @@ class RayQuery:
 class Renderer:
     """Persistent renderer (scene + ray buffers resident in HBM)."""
 
-    def __init__(self, scene, sort=True, device=0, counters=False, tiles=None):
+    def __init__(self, scene, sort=True, device=0, counters=False, tiles=None, L=None):
+        """L = the library to call (default lib(); tests: test_lib())."""
+        self.L = L or lib()
         self.scene = scene
         o = default_opts(sort, device, counters=counters, tiles=tiles)
         h = P()
-        _check(lib().rt_renderer_create(scene.ptr, C.byref(o), C.byref(h)))
+        self._check(self.L.rt_renderer_create(scene.ptr, C.byref(o), C.byref(h)))
         self.h = h
+
+    def _check(self, rc):
+        _check(rc, self.L)
 
     def run(self, pass_begin=0, count=1, stride=1, d_pass_sums=None):
         st = RtStats()
-        _check(lib().rt_renderer_run(self.h, pass_begin, count, stride,
+        self._check(self.L.rt_renderer_run(self.h, pass_begin, count, stride,
                                      P(d_pass_sums) if d_pass_sums else None, C.byref(st)))
         return st.as_dict()
 
     def run_async(self, pass_begin=0, count=1, stride=1, d_pass_sums=None):
         """rt_renderer_run_async: enqueue the passes and return; then wait_pass / finish."""
-        f = lib().rt_renderer_run_async
+        f = self.L.rt_renderer_run_async
         f.argtypes = [P, I32, I32, I32, P]
-        _check(f(self.h, pass_begin, count, stride, P(d_pass_sums) if d_pass_sums else None))
+        self._check(f(self.h, pass_begin, count, stride, P(d_pass_sums) if d_pass_sums else None))
 
     def wait_pass(self, k, hip_stream):
         """The HIP stream `hip_stream` (a raw handle, e.g. torch.cuda.current_stream().cuda_stream)
         waits until pass k of the async run has written its sums."""
-        f = lib().rt_renderer_wait_pass
+        f = self.L.rt_renderer_wait_pass
         f.argtypes = [P, I32, P]
-        _check(f(self.h, int(k), P(hip_stream) if hip_stream else None))
+        self._check(f(self.h, int(k), P(hip_stream) if hip_stream else None))
 
     def finish(self):
         st = RtStats()
-        f = lib().rt_renderer_finish
+        f = self.L.rt_renderer_finish
         f.argtypes = [P, P]
-        _check(f(self.h, C.byref(st)))
+        self._check(f(self.h, C.byref(st)))
         return st.as_dict()
 
     def run_host(self, pass_begin=0, count=1, stride=1):
         """Renders passes and returns their per-pass sums (count, W*H*3) in host memory."""
         out = np.zeros((count, self.scene.pixels * 3), np.float32)
         st = RtStats()
-        _check(lib().rt_renderer_run_host(self.h, pass_begin, count, stride, _ptr(out), C.byref(st)))
+        self._check(self.L.rt_renderer_run_host(self.h, pass_begin, count, stride, _ptr(out), C.byref(st)))
         return out, st.as_dict()
 
     def set_exchange(self, exchange=None, c_fn=None, user=None):
@@ -1370,11 +1376,11 @@ class Renderer:
         on_device = 0), or c_fn/user: a native rt_exchange_fn (a ctypes function pointer, e.g. from
         a loaded library) called with the device pointer and the pass's HIP stream (on_device = 1),
         which must enqueue its in-place sum on that stream."""
-        f = lib().rt_renderer_set_exchange
+        f = self.L.rt_renderer_set_exchange
         if c_fn is not None:
             f.argtypes = [P, P, P, I32]
             self._exchange = (c_fn, user)   # kept alive as long as the renderer
-            _check(f(self.h, C.cast(c_fn, P), P(user) if user else None, 1))
+            self._check(f(self.h, C.cast(c_fn, P), P(user) if user else None, 1))
             return
 
         def cb(user, p, n, stream):
@@ -1385,62 +1391,62 @@ class Renderer:
                 return -1
         self._exchange = EXCHANGE(cb)  # kept alive as long as the renderer
         f.argtypes = [P, EXCHANGE, P, I32]
-        _check(f(self.h, self._exchange, None, 0))
+        self._check(f(self.h, self._exchange, None, 0))
 
     def set_exchange_rccl(self, unique_id, nranks, rank):
         """The exchange over an RCCL communicator the renderer joins (one process per GPU):
         rt_renderer_set_exchange_rccl.  unique_id: the RT_RCCL_ID_BYTES bytes rank 0 got from
         rccl_unique_id(), the same on every rank.  Blocks until every rank has joined."""
-        f = lib().rt_renderer_set_exchange_rccl
+        f = self.L.rt_renderer_set_exchange_rccl
         f.argtypes = [P, P, I32, I32]
         buf = (C.c_uint8 * RCCL_ID_BYTES).from_buffer_copy(bytes(unique_id))
-        _check(f(self.h, buf, int(nranks), int(rank)))
+        self._check(f(self.h, buf, int(nranks), int(rank)))
 
     def set_counters(self, on):
-        _check(lib().rt_renderer_set_counters(self.h, int(on)))
+        self._check(self.L.rt_renderer_set_counters(self.h, int(on)))
 
     def set_accumulate(self, on):
         """Framebuffer accumulation (rt_renderer_set_accumulate; default on).  Off: runs need d_pass_sums
         and only write them (the multi-GPU drivers add the pass slices themselves)."""
-        f = lib().rt_renderer_set_accumulate
+        f = self.L.rt_renderer_set_accumulate
         f.argtypes = [P, I32]
-        _check(f(self.h, int(on)))
+        self._check(f(self.h, int(on)))
 
     def launch_profile(self, cap=256):
         """Per trace launch of the last event-timed run's first pass: [(span ms, live rays), ...]
         (rt_renderer_launch_profile)."""
-        f = lib().rt_renderer_launch_profile
+        f = self.L.rt_renderer_launch_profile
         f.argtypes = [P, I32, P, P]
         ms = np.zeros(cap, np.float64)
         live = np.zeros(cap, np.uint32)
         n = f(self.h, cap, _ptr(ms), _ptr(live))
         if n < 0:
-            _check(n)
+            self._check(n)
         return [(float(ms[b]), int(live[b])) for b in range(n)]
 
     def set_event_timing(self, on):
         """Per-bounce HIP events for process_ms / sort_ms (default on; off is ~2 % faster)."""
-        f = lib().rt_renderer_set_event_timing
+        f = self.L.rt_renderer_set_event_timing
         f.argtypes = [P, I32]
-        _check(f(self.h, int(on)))
+        self._check(f(self.h, int(on)))
 
     def framebuffer(self):
         fb = np.zeros(self.scene.pixels * 3, np.float32)
-        _check(lib().rt_renderer_read_framebuffer(self.h, _ptr(fb)))
+        self._check(self.L.rt_renderer_read_framebuffer(self.h, _ptr(fb)))
         return fb
 
     def copy_framebuffer(self, d_out):
         """Device framebuffer -> device pointer d_out (W*H*3 float32 on the renderer's device)."""
-        f = lib().rt_renderer_copy_framebuffer
+        f = self.L.rt_renderer_copy_framebuffer
         f.argtypes = [P, P]
-        _check(f(self.h, P(d_out)))
+        self._check(f(self.h, P(d_out)))
 
     def clear(self):
-        _check(lib().rt_renderer_clear(self.h))
+        self._check(self.L.rt_renderer_clear(self.h))
 
     def close(self):
         if getattr(self, "h", None):
-            lib().rt_renderer_destroy(self.h)
+            self.L.rt_renderer_destroy(self.h)
             self.h = None
 
     def __del__(self):

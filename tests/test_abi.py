@@ -74,10 +74,17 @@ def test_invalid_arguments_fail_loudly():
 
 def test_test_hooks_only_in_the_test_build():
     """The one-GPU loopback transport and the failure injection are compiled into librtamd_test.so only
-    (-DRTAMD_TEST_HOOKS): no environment variable can switch the product library's collectives."""
-    for var in (b"RTAMD_MULTI_LOOPBACK", b"RTAMD_FAIL_AFTER_SETUP"):
-        assert var not in open(R.LIB_PATH, "rb").read()
-        assert var in open(R.TEST_LIB_PATH, "rb").read()
+    (-DRTAMD_TEST_HOOKS): no environment variable can switch the product library's collectives.  The same holds
+    for the reorder's test cap on its grids and the direct entry points to the reorder kernels."""
+    product, test = open(R.LIB_PATH, "rb").read(), open(R.TEST_LIB_PATH, "rb").read()
+    hooks = (b"rtamd_test_reorder_plain", b"rtamd_test_reorder_global", b"rtamd_test_tile_bytes", b"rtamd_test_fastdiv")
+    for var in (b"RTAMD_MULTI_LOOPBACK", b"RTAMD_FAIL_AFTER_SETUP", b"RTAMD_TEST_SORT_GRID", b"fastdiv_test_kernel") + hooks:
+        assert var not in product
+        assert var in test
+    assert b"rtamd_test_" not in product
+    exported = subprocess.run(["nm", "-D", "--defined-only", R.TEST_LIB_PATH], capture_output=True, text=True,
+                              check=True).stdout.split()
+    assert all(h.decode() in exported for h in hooks)
     assert R.test_lib().rt_abi_version() == R.lib().rt_abi_version()
 
 

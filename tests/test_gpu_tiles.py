@@ -89,8 +89,9 @@ SORT_ON_CASES = [("cornell_plus", (48, 40, 45, 6), 8, 2),
                  ("cornell", (24, 16, 8, 4), 8, 3)]      # 2 stripes, 3 owners: owner 2 has none
 
 
-def render_owners(path, image, rows, owners, exchange):
-    """`owners` tile renderers on this GPU, one per tile owner, each in its own thread, with sort on;
+def render_owners(path, image, rows, owners, exchange, L=None):
+    """`owners` tile renderers on this GPU, one per tile owner, each in its own thread, with sort on, through the
+    library L (default: the product library);
     exchange = "host" (a numpy sum through the host-buffer callback) or "device" (the device-side
     group sum of tests/native/xchg.hip on the pass streams, the stream contract of the library's
     RCCL path).  Returns the owners' framebuffers summed (disjoint pixels) and their stats."""
@@ -112,7 +113,7 @@ def render_owners(path, image, rows, owners, exchange):
 
     def run(i):
         try:
-            r = R.Renderer(sc, sort=True, tiles=(owners, i, rows))
+            r = R.Renderer(sc, sort=True, tiles=(owners, i, rows), L=L)
             if group:
                 group.attach(r, i)
             else:
