@@ -20,6 +20,8 @@
 // allocates them (children of the k-th split node in depth-first order get 2k+1 and 2k+2), and
 // applies the final triangle permutation.
 #include "rt_abi.h"
+#include "rt_host.h"
+#include "mesh_ingest.h"
 
 #include <hip/hip_runtime.h>
 
@@ -32,10 +34,6 @@
 #include <vector>
 
 #pragma clang fp contract(off)
-
-namespace rtamd {
-int fail(int code, const std::string &msg);
-}
 
 namespace {
 
@@ -687,29 +685,56 @@ struct TreeNode {                       // host-side node of the build
     int child = -1;                     // first of the two children in `tree` (-1: leaf)
 };
 
-}  // namespace
+using clk = std::chrono::high_resolution_clock;
 
-namespace rtamd {
-
-// The reference's generate_bvh (scene.cu:1002-1036) up to the triangle post-processing: tris in
-// build representation (p1, p2, p3, centroid) and their material indices are permuted in place,
-// nodes receives the node array.  max_depth 30 (BVH) or 0 (no_bvh).
-int gpu_build_bvh(std::vector<rt_triangle> &tris, uint16_t *tri_mats, std::vector<rt_bvh_node> &nodes,
-                  int max_depth, int device) {
-    const int n = (int)tris.size();
-    using clk = std::chrono::high_resolution_clock;
-    const bool timing = std::getenv("RTAMD_TIMING") != nullptr;
-    auto t_mark = clk::now();
+struct Timing {                         // RTAMD_TIMING: the build's phases on stderr
+    const bool on = std::getenv("RTAMD_TIMING") != nullptr;
+    clk::time_point t_mark = clk::now();
     std::string report;
-    auto mark = [&](const char *what) {
-        if (!timing) return;
+    void mark(const char *what) {
+        if (!on) return;
         const auto now = clk::now();
         char buf[96];
         std::snprintf(buf, sizeof(buf), " %s %.2f ms,", what, std::chrono::duration<double, std::milli>(now - t_mark).count());
         report += buf;
         t_mark = now;
-    };
-    BCHK(hipSetDevice(device));
+    }
+};
+
+// The build's device buffers, sized by each call: per-triangle boxes, centroids and the order array the levels
+// permute (blo/bhi/cen/idx), their partition scratch, and the per-level node and chunk tables.
+struct BuildBuffers {
+    Buf<float4> blo, bhi, cen, t_blo, t_bhi, t_cen;
+    Buf<uint32_t> idx, t_idx;
+    Buf<int> xk, rk;
+    Buf<uint8_t> side;
+    Buf<NodeRange> d_nodes;
+    Buf<NodeOut> d_out;
+    Buf<Chunk> d_chunks;
+    Buf<int2> d_huge;
+    Buf<BoxPartial> pbox;
+    Buf<BinPartial> pbin;
+    Buf<PartCounts> pcnt;
+    int alloc(int n) {
+        const size_t m = std::max(n, 1);
+        BCHK(blo.alloc(m)); BCHK(bhi.alloc(m)); BCHK(cen.alloc(m));
+        BCHK(t_blo.alloc(m)); BCHK(t_bhi.alloc(m)); BCHK(t_cen.alloc(m));
+        BCHK(idx.alloc(m)); BCHK(t_idx.alloc(m)); BCHK(xk.alloc(m)); BCHK(rk.alloc(m)); BCHK(side.alloc(m));
+        // a level holds at most n / 1 nodes (ranges are disjoint and non-empty below the root)
+        BCHK(d_nodes.alloc(m)); BCHK(d_out.alloc(m));
+        // chunks of the huge nodes of a level: disjoint ranges of > kHuge triangles, so fewer than
+        // n / kChunk + n / kHuge of them
+        const size_t max_chunks = (size_t)n / kChunk + (size_t)n / kHuge + 1;
+        BCHK(d_chunks.alloc(max_chunks)); BCHK(d_huge.alloc(max_chunks));
+        BCHK(pbox.alloc(max_chunks)); BCHK(pbin.alloc(max_chunks)); BCHK(pcnt.alloc(max_chunks));
+        return RT_OK;
+    }
+};
+
+// Upload: the host pre-pass over triangles in build representation (p1, p2, p3, centroid) and its copy into
+// blo/bhi/cen/idx.
+int upload_triangles(const std::vector<rt_triangle> &tris, BuildBuffers &b, hipStream_t s) {
+    const int n = (int)tris.size();
     // per-triangle boxes as the reference grows them (p1, p2, p3 in turn), centroids
     std::vector<float4> h_lo(std::max(n, 1)), h_hi(std::max(n, 1)), h_cen(std::max(n, 1));
     auto mn = [](float a, float b) { return a != a ? b : (b != b ? a : (b < a ? b : a)); };
@@ -728,40 +753,33 @@ int gpu_build_bvh(std::vector<rt_triangle> &tris, uint16_t *tri_mats, std::vecto
     }
     std::vector<uint32_t> h_idx(std::max(n, 1));
     for (int i = 0; i < n; i++) h_idx[i] = (uint32_t)i;
-    Buf<float4> blo, bhi, cen, t_blo, t_bhi, t_cen;
-    Buf<uint32_t> idx, t_idx;
-    Buf<int> xk, rk;
-    Buf<uint8_t> side;
-    Buf<NodeRange> d_nodes;
-    Buf<NodeOut> d_out;
-    Buf<Chunk> d_chunks;
-    Buf<int2> d_huge;
-    Buf<BoxPartial> pbox;
-    Buf<BinPartial> pbin;
-    Buf<PartCounts> pcnt;
     const size_t m = std::max(n, 1);
-    BCHK(blo.alloc(m)); BCHK(bhi.alloc(m)); BCHK(cen.alloc(m));
-    BCHK(t_blo.alloc(m)); BCHK(t_bhi.alloc(m)); BCHK(t_cen.alloc(m));
-    BCHK(idx.alloc(m)); BCHK(t_idx.alloc(m)); BCHK(xk.alloc(m)); BCHK(rk.alloc(m)); BCHK(side.alloc(m));
-    // a level holds at most n / 1 nodes (ranges are disjoint and non-empty below the root)
-    BCHK(d_nodes.alloc(m)); BCHK(d_out.alloc(m));
-    // chunks of the huge nodes of a level: disjoint ranges of > kHuge triangles, so fewer than
-    // n / kChunk + n / kHuge of them
-    const size_t max_chunks = (size_t)n / kChunk + (size_t)n / kHuge + 1;
-    BCHK(d_chunks.alloc(max_chunks)); BCHK(d_huge.alloc(max_chunks));
-    BCHK(pbox.alloc(max_chunks)); BCHK(pbin.alloc(max_chunks)); BCHK(pcnt.alloc(max_chunks));
+    BCHK(hipMemcpyAsync(b.blo.p, h_lo.data(), m * sizeof(float4), hipMemcpyHostToDevice, s));
+    BCHK(hipMemcpyAsync(b.bhi.p, h_hi.data(), m * sizeof(float4), hipMemcpyHostToDevice, s));
+    BCHK(hipMemcpyAsync(b.cen.p, h_cen.data(), m * sizeof(float4), hipMemcpyHostToDevice, s));
+    BCHK(hipMemcpyAsync(b.idx.p, h_idx.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    BCHK(hipStreamSynchronize(s));
+    return RT_OK;
+}
+
+// The level loop over the device buffers: blo/bhi/cen/idx hold the n triangles in input order on entry and in the
+// reference's final order on return; tree receives the nodes (boxes, ranges, children).
+int build_levels(BuildBuffers &B, int n, int max_depth, hipStream_t s, std::vector<TreeNode> &tree, Timing &tm) {
+    const bool timing = tm.on;
+    auto &blo = B.blo, &bhi = B.bhi, &cen = B.cen, &t_blo = B.t_blo, &t_bhi = B.t_bhi, &t_cen = B.t_cen;
+    auto &idx = B.idx, &t_idx = B.t_idx;
+    auto &xk = B.xk, &rk = B.rk;
+    auto &side = B.side;
+    auto &d_nodes = B.d_nodes;
+    auto &d_out = B.d_out;
+    auto &d_chunks = B.d_chunks;
+    auto &d_huge = B.d_huge;
+    auto &pbox = B.pbox;
+    auto &pbin = B.pbin;
+    auto &pcnt = B.pcnt;
     std::vector<Chunk> h_chunks;
     std::vector<int2> h_huge;
-    // the per-thread default stream: the build is synchronous, and a stream costs ~3.6 ms to create
-    hipStream_t s = hipStreamPerThread;
-    BCHK(hipMemcpyAsync(blo.p, h_lo.data(), m * sizeof(float4), hipMemcpyHostToDevice, s));
-    BCHK(hipMemcpyAsync(bhi.p, h_hi.data(), m * sizeof(float4), hipMemcpyHostToDevice, s));
-    BCHK(hipMemcpyAsync(cen.p, h_cen.data(), m * sizeof(float4), hipMemcpyHostToDevice, s));
-    BCHK(hipMemcpyAsync(idx.p, h_idx.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-
-    BCHK(hipStreamSynchronize(s));
-    mark("setup+upload");
-    std::vector<TreeNode> tree(1);
+    tree.assign(1, TreeNode{});
     tree[0].begin = 0;
     tree[0].end = n;
     std::vector<int> level{0};                   // tree indices of the current level
@@ -859,10 +877,12 @@ int gpu_build_bvh(std::vector<rt_triangle> &tris, uint16_t *tri_mats, std::vecto
             levels_report += buf;
         }
     }
-    mark("levels");
+    tm.mark("levels");
     if (timing) std::fprintf(stderr, "gpu_build_bvh levels (depth:nodes/big/ms):%s\n", levels_report.c_str());
-    BCHK(hipMemcpyAsync(h_idx.data(), idx.p, m * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    BCHK(hipStreamSynchronize(s));
+    return RT_OK;
+}
+
+void number_nodes(const std::vector<TreeNode> &tree, std::vector<rt_bvh_node> &nodes) {
     // node numbering of the reference's recursion: a split allocates its two children at the
     // end of the array, then its first child's subtree is split, then the second's
     std::vector<int> final_of(tree.size(), -1);
@@ -893,6 +913,33 @@ int gpu_build_bvh(std::vector<rt_triangle> &tris, uint16_t *tri_mats, std::vecto
             nd.child1 = tn.end;
         }
     }
+}
+
+}  // namespace
+
+namespace rtamd {
+
+// The reference's generate_bvh (scene.cu:1002-1036) up to the triangle post-processing: tris in
+// build representation (p1, p2, p3, centroid) and their material indices are permuted in place,
+// nodes receives the node array.  max_depth 30 (BVH) or 0 (no_bvh).  order (optional) receives the
+// permutation: order[j] = the input index of the triangle at final position j.
+int gpu_build_bvh_order(std::vector<rt_triangle> &tris, uint16_t *tri_mats, std::vector<rt_bvh_node> &nodes,
+                        int max_depth, int device, std::vector<int32_t> *order) {
+    const int n = (int)tris.size();
+    Timing tm;
+    BCHK(hipSetDevice(device));
+    BuildBuffers B;
+    if (int rc = B.alloc(n)) return rc;
+    // the per-thread default stream: the build is synchronous, and a stream costs ~3.6 ms to create
+    hipStream_t s = hipStreamPerThread;
+    if (int rc = upload_triangles(tris, B, s)) return rc;
+    tm.mark("setup+upload");
+    std::vector<TreeNode> tree;
+    if (int rc = build_levels(B, n, max_depth, s, tree, tm)) return rc;
+    std::vector<uint32_t> h_idx(std::max(n, 1));
+    BCHK(hipMemcpyAsync(h_idx.data(), B.idx.p, h_idx.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    BCHK(hipStreamSynchronize(s));
+    number_nodes(tree, nodes);
     std::vector<rt_triangle> t2(tris.size());
     std::vector<uint16_t> m2(tris.size());
     for (int i = 0; i < n; i++) {
@@ -901,8 +948,65 @@ int gpu_build_bvh(std::vector<rt_triangle> &tris, uint16_t *tri_mats, std::vecto
     }
     tris.swap(t2);
     if (n) std::memcpy(tri_mats, m2.data(), n * sizeof(uint16_t));
-    mark("numbering+permute");
-    if (timing) std::fprintf(stderr, "gpu_build_bvh (%d triangles, %zu nodes):%s\n", n, nodes.size(), report.c_str());
+    if (order) order->assign(h_idx.begin(), h_idx.begin() + n);
+    tm.mark("numbering+permute");
+    if (tm.on) std::fprintf(stderr, "gpu_build_bvh (%d triangles, %zu nodes):%s\n", n, nodes.size(), tm.report.c_str());
+    return RT_OK;
+}
+
+int gpu_build_bvh(std::vector<rt_triangle> &tris, uint16_t *tri_mats, std::vector<rt_bvh_node> &nodes,
+                  int max_depth, int device) {
+    return gpu_build_bvh_order(tris, tri_mats, nodes, max_depth, device, nullptr);
+}
+
+// The same build for a mesh whose arrays are device memory (rt_scene_from_mesh_device): mesh_assemble_kernel
+// (mesh_ingest.hip) stands in for the host pre-pass and the upload, mesh_finalize_kernel for the host's permute
+// and record loop.  `validate` sees the assemble kernel's three error words before the first level runs.
+int gpu_build_mesh(const MeshDeviceInput &in, int max_depth, int (*validate)(void *, const uint32_t *err), void *user,
+                   std::vector<rt_triangle> &tris, uint16_t *tri_mats, std::vector<rt_bvh_node> &nodes,
+                   std::vector<int32_t> &face_index) {
+    const int n = in.triangle_count;
+    Timing tm;
+    BCHK(hipSetDevice(in.device));
+    // the caller's stream may still be producing the arrays
+    BCHK(hipStreamSynchronize(static_cast<hipStream_t>(in.stream)));
+    BuildBuffers B;
+    if (int rc = B.alloc(n)) return rc;
+    const size_t m = std::max(n, 1);
+    Buf<float> vrec;                    // 36 B per triangle: the gathered vertices, input order
+    Buf<uint32_t> d_err;
+    Buf<rt_triangle> d_tris;
+    Buf<uint16_t> d_mats;
+    Buf<int32_t> d_face;
+    BCHK(vrec.alloc(m * 9)); BCHK(d_err.alloc(3)); BCHK(d_tris.alloc(m)); BCHK(d_mats.alloc(m)); BCHK(d_face.alloc(m));
+    hipStream_t s = hipStreamPerThread;
+    uint32_t err[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu};
+    BCHK(hipMemsetAsync(d_err.p, 0xff, 3 * sizeof(uint32_t), s));
+    if (n) {
+        mesh_assemble_launch(in.vertices, in.vertex_count, in.indices, in.materials, in.material_count, n, B.blo.p,
+                             B.bhi.p, B.cen.p, B.idx.p, vrec.p, d_err.p, s);
+        BCHK(hipGetLastError());
+    }
+    BCHK(hipMemcpyAsync(err, d_err.p, sizeof(err), hipMemcpyDeviceToHost, s));
+    BCHK(hipStreamSynchronize(s));
+    tm.mark("setup+assemble");
+    if (int rc = validate(user, err)) return rc;
+    std::vector<TreeNode> tree;
+    if (int rc = build_levels(B, n, max_depth, s, tree, tm)) return rc;
+    tris.assign((size_t)n, rt_triangle{});
+    face_index.assign((size_t)n, 0);
+    if (n) {
+        mesh_finalize_launch(B.idx.p, vrec.p, in.materials, n, d_tris.p, d_mats.p, d_face.p, s);
+        BCHK(hipGetLastError());
+        BCHK(hipMemcpyAsync(tris.data(), d_tris.p, (size_t)n * sizeof(rt_triangle), hipMemcpyDeviceToHost, s));
+        BCHK(hipMemcpyAsync(tri_mats, d_mats.p, (size_t)n * sizeof(uint16_t), hipMemcpyDeviceToHost, s));
+        BCHK(hipMemcpyAsync(face_index.data(), d_face.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    }
+    BCHK(hipStreamSynchronize(s));
+    tm.mark("finalize+download");
+    number_nodes(tree, nodes);
+    tm.mark("numbering");
+    if (tm.on) std::fprintf(stderr, "gpu_build_mesh (%d triangles, %zu nodes):%s\n", n, nodes.size(), tm.report.c_str());
     return RT_OK;
 }
 

@@ -31,9 +31,21 @@ int fail(int code, const std::string &msg) {
     return code;
 }
 
-// GPU binned-SAH build (csrc/bvh_build.hip): same output as BvhBuilder below.
-int gpu_build_bvh(std::vector<rt_triangle> &tris, uint16_t *tri_mats, std::vector<rt_bvh_node> &nodes,
-                  int max_depth, int device);
+// GPU binned-SAH build (csrc/bvh_build.hip; gpu_build_bvh with the permutation handed out): same output as
+// BvhBuilder below, and order[j] = the input index of the triangle at final position j.
+// Both device builds are weak references: a host-only program (tools/experiments/*_host_check.cpp) links this
+// file without csrc/, and asking it for a device build is RT_E_NODEVICE.
+__attribute__((weak)) int gpu_build_bvh_order(std::vector<rt_triangle> &tris, uint16_t *tri_mats,
+                                              std::vector<rt_bvh_node> &nodes, int max_depth, int device,
+                                              std::vector<int32_t> *order);
+// The same build for a mesh in device memory (csrc/bvh_build.hip + csrc/mesh_ingest.hip): tris receives the
+// final ray-tracing records.  err = the assemble kernel's three words (smallest triangle with a bad vertex
+// index, with a bad material index, 2 * (smallest non-finite triangle) + (1 = centroid only)), 0xffffffff =
+// none; a non-zero return of `validate` ends the build before the first level.
+__attribute__((weak)) int gpu_build_mesh(const MeshDeviceInput &in, int max_depth,
+                                         int (*validate)(void *, const uint32_t *err), void *user,
+                                         std::vector<rt_triangle> &tris, uint16_t *tri_mats,
+                                         std::vector<rt_bvh_node> &nodes, std::vector<int32_t> &face_index);
 
 namespace {
 
@@ -76,14 +88,18 @@ struct Box {
 // (tests/test_scene_parity.py compares them with the oracle's serial restatement).
 class BvhBuilder {
 public:
-    BvhBuilder(std::vector<rt_triangle> &tris, uint16_t *tri_mats, std::vector<rt_bvh_node> &nodes)
-        : tris_(tris), mats_(tri_mats), nodes_(nodes) {}
+    // order receives order[j] = the input index of the triangle at final position j
+    BvhBuilder(std::vector<rt_triangle> &tris, uint16_t *tri_mats, std::vector<rt_bvh_node> &nodes,
+               std::vector<int32_t> &order)
+        : tris_(tris), mats_(tri_mats), nodes_(nodes), order_(order) {}
 
     void build(int max_depth, int threads) {
         const int n = (int)tris_.size();
         box_.resize(n);
         for (int a = 0; a < 3; a++) cent_[a].resize(n);
+        order_.resize(n);
         for (int i = 0; i < n; i++) {
+            order_[i] = i;
             box_[i] = Box();
             box_[i].grow(tris_[i]);
             cent_[0][i] = tris_[i].normal.x;
@@ -106,6 +122,7 @@ private:
     std::vector<rt_triangle> &tris_;
     uint16_t *mats_;
     std::vector<rt_bvh_node> &nodes_;
+    std::vector<int32_t> &order_;          // a side array like box_ and cent_: subtrees own disjoint ranges of it
     std::vector<Box> box_;
     std::vector<float> cent_[3];
     std::atomic<int> spare_threads_{0};
@@ -195,6 +212,7 @@ private:
                 std::swap(tris_[i], tris_[j]);
                 std::swap(mats_[i], mats_[j]);
                 std::swap(box_[i], box_[j]);
+                std::swap(order_[i], order_[j]);
                 for (int a = 0; a < 3; a++) std::swap(cent_[a][i], cent_[a][j]);
                 j--;
             }
@@ -356,7 +374,159 @@ int load_pfm(const std::string &path, std::vector<rt_vec3> &env, int &w, int &h)
     return RT_OK;
 }
 
+bool finite3(rt_vec3 p) { return std::isfinite(p.x) && std::isfinite(p.y) && std::isfinite(p.z); }
+
+// Both BVH builders bin by (int)((centroid - min_centroid) * scale) (scene.cu:916): with a NaN or
+// infinite coordinate, or vertices whose sum overflows, that product is NaN, and its conversion is
+// undefined behaviour in the reference (an out-of-bounds bin on x86).  Such a scene has no answer to
+// agree with, so it is refused, before either builder runs.
+int check_spheres(const rt_scene_host *s) {
+    for (size_t i = 0; i < s->spheres.size(); i++)
+        if (!finite3(s->spheres[i].center) || !std::isfinite(s->spheres[i].radius))
+            return fail(RT_E_INVALID, "sphere " + std::to_string(i) + " has a non-finite coordinate or radius");
+    return RT_OK;
+}
+int non_finite_triangle(size_t i, bool centroid_only) {
+    if (!centroid_only) return fail(RT_E_INVALID, "triangle " + std::to_string(i) + " has a non-finite coordinate");
+    return fail(RT_E_INVALID, "triangle " + std::to_string(i) + " has a non-finite centroid: the sum "
+                              "of its vertices overflows");
+}
+int check_triangles(const rt_scene_host *s) {
+    for (size_t i = 0; i < s->triangles.size(); i++) {
+        const rt_triangle &tr = s->triangles[i];
+        if (!finite3(tr.p1) || !finite3(tr.p2p1) || !finite3(tr.p3p1)) return non_finite_triangle(i, false);
+        if (!finite3(tr.normal)) return non_finite_triangle(i, true);
+    }
+    return RT_OK;
+}
+
+// What the device build's assemble kernel found (its three words), refused as the host entry refuses it.
+struct DeviceMeshCheck {
+    const rt_scene_host *s;
+    const MeshDeviceInput *dm;
+};
+int check_device_mesh(void *user, const uint32_t *err) {
+    const DeviceMeshCheck &c = *static_cast<const DeviceMeshCheck *>(user);
+    if (err[1] != 0xffffffffu) return mesh_bad_material("triangle", err[1], c.dm->material_count);
+    if (err[0] != 0xffffffffu) return mesh_bad_vertex_index(err[0], c.dm->vertex_count);
+    if (int rc = check_spheres(c.s)) return rc;
+    if (err[2] != 0xffffffffu) return non_finite_triangle(err[2] >> 1, err[2] & 1);
+    return RT_OK;
+}
+
 }  // namespace
+
+int mesh_bad_material(const char *what, int64_t i, int32_t material_count) {
+    return fail(RT_E_INVALID, std::string(what) + " " + std::to_string(i) + " has a material index outside the table of " +
+                                  std::to_string(material_count) + " materials");
+}
+int mesh_bad_vertex_index(int64_t i, int32_t vertex_count) {
+    return fail(RT_E_INVALID, "triangle " + std::to_string(i) + " has a vertex index outside [0, " +
+                                  std::to_string(vertex_count) + ")");
+}
+
+void scene_defaults(rt_scene &v) {
+    v.width = 1920;                                   // scene.cu:571-574
+    v.height = 1080;
+    v.ray_count = 1;
+    v.bounces = 3;
+}
+
+int apply_image_opts(rt_scene &v, const rt_load_opts &opts) {
+    if (opts.image_override) {
+        v.width = opts.width;
+        v.height = opts.height;
+        v.ray_count = opts.ray_count;
+        v.bounces = opts.bounces;
+    }
+    if (opts.exposure_override) v.exposure = opts.exposure;
+    if (v.width < 2 || v.height < 2 || v.ray_count < 0 || v.bounces < 0)
+        return fail(RT_E_INVALID, "scene image must be at least 2x2 with non-negative spp/bounces");
+    return RT_OK;
+}
+
+int finish_scene(rt_scene_host *s, const rt_load_opts &opts, bool have_env, const std::vector<uint16_t> &sphere_mats,
+                 const std::vector<uint16_t> &tri_mats, const MeshDeviceInput *dm) {
+    rt_scene &v = s->view;
+    if (int rc = apply_image_opts(v, opts)) return rc;
+    if (!have_env) {                                  // reference reads an unset map: UB
+        s->env.assign(1, rt_vec3{0, 0, 0});
+        v.environment_map_width = v.environment_map_height = 1;
+    }
+    const size_t tri_count = dm ? (size_t)dm->triangle_count : s->triangles.size();
+    if (s->spheres.size() + tri_count > 0x7fffffff || s->materials.size() > 65535)
+        return fail(RT_E_INVALID, "scene too large");
+    s->material_indices = sphere_mats;
+    if (dm) s->material_indices.resize(sphere_mats.size() + tri_count, 0);
+    else s->material_indices.insert(s->material_indices.end(), tri_mats.begin(), tri_mats.end());
+    if (!dm) {
+        if (int rc = check_spheres(s)) return rc;
+        if (int rc = check_triangles(s)) return rc;
+    }
+
+    // Camera precompute (scene.cu:62-76).
+    const rt_vec3 right = cross(v.up, v.forward);
+    const float nph = 2.0f * std::tan(v.vertical_fov * 0.5f);
+    const float npw = nph * v.width / v.height;
+    v.scaled_right = scale(npw, right);
+    v.scaled_up = scale(nph, v.up);
+    v.near_plane_top_left = add(sub(v.forward, scale(0.5f, v.scaled_right)), scale(0.5f, v.scaled_up));
+    v.inv_width = 1.0f / (v.width - 1);
+    v.inv_height = 1.0f / (v.height - 1);
+
+    // BVH (scene.cu:1002-1036), then the ray-tracing triangle representation.
+    const auto t0 = std::chrono::high_resolution_clock::now();
+    uint16_t *tri_mat_out = s->material_indices.data() + s->spheres.size();
+    const int max_depth = opts.use_bvh ? 30 : 0;
+    if ((dm && !gpu_build_mesh) || (!dm && opts.bvh_device >= 0 && !gpu_build_bvh_order))
+        return fail(RT_E_NODEVICE, "this build has no device BVH builder");
+    if (dm) {
+        DeviceMeshCheck check{s, dm};
+        if (int rc = gpu_build_mesh(*dm, max_depth, check_device_mesh, &check, s->triangles, tri_mat_out, s->bvh,
+                                    s->face_index))
+            return rc;
+    } else if (opts.bvh_device >= 0) {
+        if (int rc = gpu_build_bvh_order(s->triangles, tri_mat_out, s->bvh, max_depth, opts.bvh_device, &s->face_index))
+            return rc;
+    } else {
+        BvhBuilder(s->triangles, tri_mat_out, s->bvh, s->face_index).build(max_depth, bvh_threads());
+    }
+    const auto t1 = std::chrono::high_resolution_clock::now();
+    s->bvh_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    if (!opts.quiet) {
+        std::printf("Triangle count: %zu\n", s->triangles.size());
+        std::printf("BVH Took %gms\n", s->bvh_ms);
+        std::printf("Node count: %zu\n", s->bvh.size());
+    }
+    if (!dm)                                          // the device build's finalize kernel wrote the records
+        for (auto &tr : s->triangles) {
+            tr.p2p1 = sub(tr.p2p1, tr.p1);
+            tr.p3p1 = sub(tr.p3p1, tr.p1);
+            tr.normal = normalise(cross(tr.p3p1, tr.p2p1));
+        }
+    // Reorder-key bounds (scene.cu:822-830): note inv_dimensions = 1 / max, not 1 / (max - min).
+    v.min_coord = s->bvh[0].min_bound;
+    rt_vec3 mx = s->bvh[0].max_bound;
+    for (const auto &sp : s->spheres) {
+        const rt_vec3 r{sp.radius, sp.radius, sp.radius};
+        mx = vmax(mx, add(sp.center, r));
+        v.min_coord = vmin(v.min_coord, sub(sp.center, r));
+    }
+    v.inv_dimensions = {1 / mx.x, 1 / mx.y, 1 / mx.z};
+
+    v.spheres = s->spheres.data();
+    v.sphere_count = (int32_t)s->spheres.size();
+    v.triangles = s->triangles.data();
+    v.triangle_count = (int32_t)s->triangles.size();
+    v.material_indices = s->material_indices.data();
+    v.materials = s->materials.data();
+    v.material_count = (int32_t)s->materials.size();
+    v.bvh = s->bvh.data();
+    v.bvh_node_count = (int32_t)s->bvh.size();
+    v.environment_map = s->env.data();
+    return RT_OK;
+}
+
 }  // namespace rtamd
 
 using namespace rtamd;
@@ -378,10 +548,7 @@ int rt_scene_load(const char *path, const rt_load_opts *opts_in, rt_scene_host *
     if (!file) return fail(RT_E_IO, std::string("cannot open scene file '") + path + "'");
     auto s = new rt_scene_host();
     rt_scene &v = s->view;
-    v.width = 1920;                                   // scene.cu:571-574
-    v.height = 1080;
-    v.ray_count = 1;
-    v.bounces = 3;
+    scene_defaults(v);
     std::unordered_map<std::string, uint16_t> mat_ids;
     std::vector<uint16_t> sphere_mats, tri_mats;
     bool have_env = false;
@@ -472,98 +639,19 @@ int rt_scene_load(const char *path, const rt_load_opts *opts_in, rt_scene_host *
             v.exposure = fnum(t, 5);
         }
     }
-    if (opts.image_override) {
-        v.width = opts.width;
-        v.height = opts.height;
-        v.ray_count = opts.ray_count;
-        v.bounces = opts.bounces;
-    }
-    if (opts.exposure_override) v.exposure = opts.exposure;
-    if (v.width < 2 || v.height < 2 || v.ray_count < 0 || v.bounces < 0)
-        return bad(fail(RT_E_INVALID, "scene image must be at least 2x2 with non-negative spp/bounces"));
-    if (!have_env) {                                  // reference reads an unset map: UB
-        s->env.assign(1, rt_vec3{0, 0, 0});
-        v.environment_map_width = v.environment_map_height = 1;
-    }
-    if (s->spheres.size() + s->triangles.size() > 0x7fffffff || s->materials.size() > 65535)
-        return bad(fail(RT_E_INVALID, "scene too large"));
-    s->material_indices = sphere_mats;
-    s->material_indices.insert(s->material_indices.end(), tri_mats.begin(), tri_mats.end());
-    // Both BVH builders bin by (int)((centroid - min_centroid) * scale) (scene.cu:916): with a NaN or
-    // infinite coordinate, or vertices whose sum overflows, that product is NaN, and its conversion is
-    // undefined behaviour in the reference (an out-of-bounds bin on x86).  Such a scene has no answer to
-    // agree with, so it is refused here, before either builder runs.
-    auto finite3 = [](rt_vec3 p) { return std::isfinite(p.x) && std::isfinite(p.y) && std::isfinite(p.z); };
-    for (size_t i = 0; i < s->spheres.size(); i++)
-        if (!finite3(s->spheres[i].center) || !std::isfinite(s->spheres[i].radius))
-            return bad(fail(RT_E_INVALID, "sphere " + std::to_string(i) + " has a non-finite coordinate or radius"));
-    for (size_t i = 0; i < s->triangles.size(); i++) {
-        const rt_triangle &tr = s->triangles[i];
-        if (!finite3(tr.p1) || !finite3(tr.p2p1) || !finite3(tr.p3p1))
-            return bad(fail(RT_E_INVALID, "triangle " + std::to_string(i) + " has a non-finite coordinate"));
-        if (!finite3(tr.normal))
-            return bad(fail(RT_E_INVALID, "triangle " + std::to_string(i) + " has a non-finite centroid: the sum "
-                                          "of its vertices overflows"));
-    }
-
-    // Camera precompute (scene.cu:62-76).
-    const rt_vec3 right = cross(v.up, v.forward);
-    const float nph = 2.0f * std::tan(v.vertical_fov * 0.5f);
-    const float npw = nph * v.width / v.height;
-    v.scaled_right = scale(npw, right);
-    v.scaled_up = scale(nph, v.up);
-    v.near_plane_top_left = add(sub(v.forward, scale(0.5f, v.scaled_right)), scale(0.5f, v.scaled_up));
-    v.inv_width = 1.0f / (v.width - 1);
-    v.inv_height = 1.0f / (v.height - 1);
-
-    // BVH (scene.cu:1002-1036), then the ray-tracing triangle representation.
-    const auto t0 = std::chrono::high_resolution_clock::now();
-    if (opts.bvh_device >= 0) {
-        if (int rc = rtamd::gpu_build_bvh(s->triangles, s->material_indices.data() + s->spheres.size(), s->bvh,
-                                          opts.use_bvh ? 30 : 0, opts.bvh_device))
-            return bad(rc);
-    } else {
-        BvhBuilder(s->triangles, s->material_indices.data() + s->spheres.size(), s->bvh)
-            .build(opts.use_bvh ? 30 : 0, bvh_threads());
-    }
-    const auto t1 = std::chrono::high_resolution_clock::now();
-    s->bvh_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
-    if (!opts.quiet) {
-        std::printf("Triangle count: %zu\n", s->triangles.size());
-        std::printf("BVH Took %gms\n", s->bvh_ms);
-        std::printf("Node count: %zu\n", s->bvh.size());
-    }
-    for (auto &tr : s->triangles) {
-        tr.p2p1 = sub(tr.p2p1, tr.p1);
-        tr.p3p1 = sub(tr.p3p1, tr.p1);
-        tr.normal = normalise(cross(tr.p3p1, tr.p2p1));
-    }
-    // Reorder-key bounds (scene.cu:822-830): note inv_dimensions = 1 / max, not 1 / (max - min).
-    v.min_coord = s->bvh[0].min_bound;
-    rt_vec3 mx = s->bvh[0].max_bound;
-    for (const auto &sp : s->spheres) {
-        const rt_vec3 r{sp.radius, sp.radius, sp.radius};
-        mx = vmax(mx, add(sp.center, r));
-        v.min_coord = vmin(v.min_coord, sub(sp.center, r));
-    }
-    v.inv_dimensions = {1 / mx.x, 1 / mx.y, 1 / mx.z};
-
-    v.spheres = s->spheres.data();
-    v.sphere_count = (int32_t)s->spheres.size();
-    v.triangles = s->triangles.data();
-    v.triangle_count = (int32_t)s->triangles.size();
-    v.material_indices = s->material_indices.data();
-    v.materials = s->materials.data();
-    v.material_count = (int32_t)s->materials.size();
-    v.bvh = s->bvh.data();
-    v.bvh_node_count = (int32_t)s->bvh.size();
-    v.environment_map = s->env.data();
+    if (int rc = finish_scene(s, opts, have_env, sphere_mats, tri_mats, nullptr)) return bad(rc);
     *out = s;
     return RT_OK;
 }
 
 const rt_scene *rt_scene_view(const rt_scene_host *s) { return s ? &s->view : nullptr; }
 double rt_scene_bvh_ms(const rt_scene_host *s) { return s ? s->bvh_ms : 0.0; }
+int rt_scene_face_index(const rt_scene_host *s, const int32_t **index_out, int32_t *count_out) {
+    if (!s || !index_out || !count_out) return fail(RT_E_INVALID, "rt_scene_face_index: null argument");
+    *index_out = s->face_index.data();
+    *count_out = (int32_t)s->face_index.size();
+    return RT_OK;
+}
 void rt_scene_free(rt_scene_host *s) { delete s; }
 const char *rt_last_error(void) { return g_error.c_str(); }
 int rt_abi_version(void) { return RT_ABI_VERSION; }

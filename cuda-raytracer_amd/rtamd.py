@@ -57,6 +57,18 @@ class RtLoadOpts(C.Structure):
                 ("exposure_override", I32), ("exposure", C.c_float), ("bvh_device", I32)]
 
 
+class RtCameraDesc(C.Structure):
+    """rt_camera_desc: the `camera` line of a scene file."""
+    _fields_ = [("position", Vec3), ("forward", Vec3), ("up", Vec3), ("vertical_fov_degrees", C.c_float)]
+
+
+class RtMeshDesc(C.Structure):
+    """rt_mesh_desc: a scene as arrays (rt_scene_from_mesh)."""
+    _fields_ = [("vertices", P), ("vertex_count", I32), ("indices", P), ("triangle_count", I32),
+                ("triangle_materials", P), ("spheres", P), ("sphere_count", I32), ("sphere_materials", P),
+                ("materials", P), ("material_count", I32), ("camera", C.POINTER(RtCameraDesc)), ("sky", C.POINTER(Vec3))]
+
+
 class RtOpts(C.Structure):
     _fields_ = [("sort", I32), ("device", I32), ("pass_begin", I32), ("pass_count", I32),
                 ("pass_stride", I32), ("collect_counters", I32),
@@ -431,8 +443,117 @@ def device_count():
     return lib().rt_device_count()
 
 
+def _mesh_np(x, what, dtype, shape_tail):
+    """A from_mesh array given as numpy: dtype and shape (n,) + shape_tail checked, made contiguous, never converted."""
+    a = np.asarray(x)
+    if a.dtype != dtype:
+        raise ValueError("%s must be %s, not %s" % (what, np.dtype(dtype).name, a.dtype))
+    if a.ndim != len(shape_tail) + 1 or tuple(a.shape[1:]) != tuple(shape_tail):
+        raise ValueError("%s must have shape (n%s), not %s" % (what, "".join(", %d" % s for s in shape_tail), a.shape))
+    return np.ascontiguousarray(a)
+
+
+def _mesh_indices_np(x, what, dtype, shape_tail):
+    """Integer indices of any integer dtype, range-checked into `dtype` (int32 vertex indices, uint16 materials)."""
+    a = np.asarray(x)
+    if a.dtype.kind not in "iu":
+        raise ValueError("%s must be an integer array, not %s" % (what, a.dtype))
+    if a.ndim != len(shape_tail) + 1 or tuple(a.shape[1:]) != tuple(shape_tail):
+        raise ValueError("%s must have shape (n%s), not %s" % (what, "".join(", %d" % s for s in shape_tail), a.shape))
+    if a.dtype != dtype and a.size:
+        info = np.iinfo(dtype)
+        if int(a.min()) < info.min or int(a.max()) > info.max:
+            raise ValueError("%s has a value outside %s" % (what, np.dtype(dtype).name))
+    return np.ascontiguousarray(a, dtype)
+
+
+def _soup_rows(shape, what="vertices"):
+    """The triangle count of soup vertices of shape (F, 9), (F, 3, 3) or (3F, 3)."""
+    if len(shape) == 2 and shape[1] == 9 or len(shape) == 3 and tuple(shape[1:]) == (3, 3):
+        return int(shape[0])
+    if len(shape) == 2 and shape[1] == 3 and shape[0] % 3 == 0:
+        return int(shape[0]) // 3
+    raise ValueError("%s of a soup (faces=None) must have shape (n, 9), (n, 3, 3) or (3n, 3), not %s" % (what, tuple(shape)))
+
+
+def _mesh_arrays(tri, m, keep):
+    """Scene.from_mesh's triangle arrays as numpy -> the descriptor's host pointers."""
+    v, f, fm = tri["vertices"], tri["faces"], tri["face_materials"]
+    v = np.asarray(v)
+    if v.dtype != np.float32:
+        raise ValueError("vertices must be float32, not %s" % v.dtype)
+    if f is None:
+        n = _soup_rows(v.shape)
+        v = np.ascontiguousarray(v).reshape(-1, 3)
+    else:
+        v = _mesh_np(v, "vertices", np.float32, (3,))
+        f = _mesh_indices_np(f, "faces", np.int32, (3,))
+        n = f.shape[0]
+        m.indices = _ptr(f)
+    m.vertices, m.vertex_count, m.triangle_count = _ptr(v), v.shape[0], n
+    if fm is not None:
+        fm = _mesh_indices_np(fm, "face_materials", np.uint16, ())
+        if fm.shape[0] != n:
+            raise ValueError("face_materials must have one entry per face (%d), not %d" % (n, fm.shape[0]))
+        m.triangle_materials = _ptr(fm)
+    keep.extend([v, f, fm])
+
+
+def _mesh_tensors(tri, on_gpu, m, keep):
+    """Scene.from_mesh's triangle arrays as torch tensors on one GPU -> the descriptor's device pointers; returns
+    the device index.  Nothing is copied except an int64 index tensor, which is range-checked and narrowed."""
+    import torch
+    given = [k for k, x in tri.items() if x is not None]
+    for k in given:
+        if k not in on_gpu:
+            raise ValueError("%s must be a tensor on the device of %s, not %s" % (k, on_gpu[0], type(tri[k]).__name__))
+    dev = tri[on_gpu[0]].device
+    for k in given:
+        x = tri[k]
+        if x.device.type != "cuda" or x.device != dev:
+            raise ValueError("%s must be on %s, not %s" % (k, dev, x.device))
+    v, f, fm = tri["vertices"], tri["faces"], tri["face_materials"]
+    if v is None:
+        raise ValueError("vertices must be given")
+    if v.dtype != torch.float32:
+        raise ValueError("vertices must be float32, not %s" % v.dtype)
+    if not v.is_contiguous():
+        raise ValueError("vertices must be contiguous")
+    if f is None:
+        n = _soup_rows(tuple(v.shape))
+        vcount = 3 * n
+    else:
+        if v.dim() != 2 or v.shape[1] != 3:
+            raise ValueError("vertices must have shape (n, 3), not %s" % (tuple(v.shape),))
+        vcount = int(v.shape[0])
+        if f.dtype not in (torch.int32, torch.int64):
+            raise ValueError("faces must be int32 or int64, not %s" % f.dtype)
+        if f.dim() != 2 or f.shape[1] != 3:
+            raise ValueError("faces must have shape (n, 3), not %s" % (tuple(f.shape),))
+        if not f.is_contiguous():
+            raise ValueError("faces must be contiguous")
+        if f.dtype == torch.int64:
+            if f.numel() and (int(f.min()) < -2 ** 31 or int(f.max()) > 2 ** 31 - 1):
+                raise ValueError("faces has a value outside int32")
+            f = f.to(torch.int32)
+        n = int(f.shape[0])
+        m.indices = P(f.data_ptr()) if n else None
+    m.vertices, m.vertex_count, m.triangle_count = (P(v.data_ptr()) if vcount else None), vcount, n
+    if fm is not None:
+        ok = [torch.int16] + ([torch.uint16] if hasattr(torch, "uint16") else [])
+        if fm.dtype not in ok:
+            raise ValueError("face_materials must be uint16 or int16, not %s" % fm.dtype)
+        if fm.dim() != 1 or int(fm.shape[0]) != n:
+            raise ValueError("face_materials must have shape (%d,), not %s" % (n, tuple(fm.shape)))
+        if not fm.is_contiguous():
+            raise ValueError("face_materials must be contiguous")
+        m.triangle_materials = P(fm.data_ptr()) if n else None
+    keep.extend([v, f, fm])
+    return dev.index if dev.index is not None else torch.cuda.current_device()
+
+
 class Scene:
-    """A scene loaded by the product loader (rt_scene_load)."""
+    """A scene loaded by the product loader (rt_scene_load), or made from arrays by from_mesh."""
 
     def __init__(self, path, use_bvh=True, asset_root=ASSETS, image=None, exposure=None, quiet=True,
                  bvh_device=-1):
@@ -456,10 +577,110 @@ class Scene:
         self.h = h
         self.view = L.rt_scene_view(h).contents
 
+    @classmethod
+    def from_mesh(cls, vertices, faces=None, materials=None, face_materials=None, spheres=None, sphere_materials=None,
+                  camera=None, sky=None, image=None, exposure=None, use_bvh=True, bvh_device=-1):
+        """rt_scene_from_mesh / rt_scene_from_mesh_device: the scene of a mesh held in arrays, byte for
+        byte what Scene(path) makes of the description's canonical scene file.
+
+        vertices  (V, 3) float32; with faces=None a soup: (F, 9), (F, 3, 3) or (3F, 3), triangle i = rows 3i..3i+2.
+        faces     (F, 3) int32; int64 is accepted and range-checked in the conversion.
+        materials (M, 12) float32 rows laid out like arrays()["materials"]; None = the loader's default material.
+        face_materials (F,), sphere_materials (S,) integers below M (None = all 0); spheres (S, 4) float32.
+        camera    (position, forward, up, fov_degrees) or None; sky (r, g, b) or None.
+        image     (width, height, spp, bounces) and exposure as Scene's.
+
+        numpy arrays and CPU tensors take the host entry (bvh_device >= 0 builds the BVH on that GPU).  If vertices,
+        faces or face_materials is a torch tensor on a GPU, all of them must be contiguous tensors on that one device
+        (float32; int32 or int64; uint16 or int16) and the device entry reads them in place, after synchronising
+        torch.cuda.current_stream(device); a bvh_device that is given must be that device.  Either way the result
+        is a host-owned Scene.
+
+        The two recipes a mesh user needs: an answer index i >= S (S = the sphere count) of any query is input
+        face `scene.face_index[i - S]`; and moving geometry goes to a RayQuery as
+        `q.update(V_new[F[scene.face_index]].reshape(-1, 9))` (V_new (V, 3), F (F, 3) long: plain indexing, numpy
+        or torch on the device)."""
+        L = lib()
+        o = RtLoadOpts()
+        L.rt_default_load_opts(C.byref(o))
+        o.use_bvh = int(use_bvh)
+        o.quiet = 1
+        if image is not None:
+            o.image_override = 1
+            o.width, o.height, o.ray_count, o.bounces = [int(v) for v in image]
+        if exposure is not None:
+            o.exposure_override = 1
+            o.exposure = float(exposure)
+        m = RtMeshDesc()
+        keep = []                                       # what the descriptor points into, alive until the call returns
+        tri = {"vertices": vertices, "faces": faces, "face_materials": face_materials}
+        tri = {k: (v.numpy() if _is_tensor(v) and v.device.type == "cpu" else v) for k, v in tri.items()}
+        on_gpu = [k for k, v in tri.items() if _is_tensor(v)]
+        stream = None
+        if on_gpu:
+            dev = _mesh_tensors(tri, on_gpu, m, keep)
+            if int(bvh_device) >= 0 and int(bvh_device) != dev:
+                raise ValueError("bvh_device %d is not the tensors' device cuda:%d" % (int(bvh_device), dev))
+            o.bvh_device = dev
+            import torch
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        else:
+            o.bvh_device = int(bvh_device)
+            _mesh_arrays(tri, m, keep)
+        if materials is not None:
+            a = _mesh_np(materials, "materials", np.float32, (12,))
+            m.materials, m.material_count = _ptr(a), a.shape[0]
+            keep.append(a)
+        if spheres is not None:
+            a = _mesh_np(spheres, "spheres", np.float32, (4,))
+            m.spheres, m.sphere_count = _ptr(a), a.shape[0]
+            keep.append(a)
+        if sphere_materials is not None:
+            a = _mesh_indices_np(sphere_materials, "sphere_materials", np.uint16, ())
+            if spheres is None or a.shape[0] != m.sphere_count:
+                raise ValueError("sphere_materials must have one entry per sphere (%d), not %d"
+                                 % (m.sphere_count, a.shape[0]))
+            m.sphere_materials = _ptr(a)
+            keep.append(a)
+        if camera is not None:
+            pos, fwd, up, fov = camera
+            cam = RtCameraDesc(Vec3(*[float(x) for x in pos]), Vec3(*[float(x) for x in fwd]),
+                               Vec3(*[float(x) for x in up]), float(fov))
+            m.camera = C.pointer(cam)
+            keep.append(cam)
+        if sky is not None:
+            sk = Vec3(*[float(x) for x in sky])
+            m.sky = C.pointer(sk)
+            keep.append(sk)
+        h = P()
+        if on_gpu:
+            L.rt_scene_from_mesh_device.argtypes = [P, P, P, C.POINTER(P)]
+            _check(L.rt_scene_from_mesh_device(C.byref(m), C.byref(o), P(stream) if stream else None, C.byref(h)))
+        else:
+            L.rt_scene_from_mesh.argtypes = [P, P, C.POINTER(P)]
+            _check(L.rt_scene_from_mesh(C.byref(m), C.byref(o), C.byref(h)))
+        self = cls.__new__(cls)
+        self._root = None
+        self.h = h
+        self.view = L.rt_scene_view(h).contents
+        return self
+
     def __del__(self):
         if getattr(self, "h", None):
             lib().rt_scene_free(self.h)
             self.h = None
+
+    @property
+    def face_index(self):
+        """rt_scene_face_index: numpy int32 (triangle_count,); entry j is the input index of scene triangle j (answer
+        index sphere_count + j of every query): the face given to from_mesh, or the triangle's position in the file."""
+        L = lib()
+        L.rt_scene_face_index.argtypes = [P, C.POINTER(C.POINTER(I32)), C.POINTER(I32)]
+        p, n = C.POINTER(I32)(), I32()
+        _check(L.rt_scene_face_index(self.h, C.byref(p), C.byref(n)))
+        if n.value == 0:
+            return np.zeros(0, np.int32)
+        return np.ctypeslib.as_array(p, shape=(n.value,)).astype(np.int32, copy=True)
 
     @property
     def ptr(self):
@@ -859,6 +1080,12 @@ class RayQuery:
         h = P()
         _check(f.rt_query_create(scene.ptr, C.byref(o), C.byref(h)), f)
         self.h = h
+
+    @classmethod
+    def from_mesh(cls, *args, device=0, counters=False, **kwargs):
+        """RayQuery(Scene.from_mesh(...), device, counters): resident queries on a mesh held in arrays.  The scene
+        stays alive as .scene; its face_index maps answer indices back to the input faces."""
+        return cls(Scene.from_mesh(*args, **kwargs), device, counters)
 
     @staticmethod
     def check_tensor(x, device, what="rays", shape_tail=(6,)):

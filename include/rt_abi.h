@@ -814,6 +814,58 @@ int rt_query_overlap_box(rt_query *q, const float *d_boxes, int32_t n, int32_t k
 int rt_query_overlap_box_host(rt_query *q, const float *boxes, int32_t n, int32_t k, const rt_overlap_out *out);
 int rt_scene_overlap_box(const rt_scene *scene, const float *boxes, int32_t n, int32_t k, const rt_overlap_out *out);
 
+/* ------------------------------------------------------------------ scenes from vertex and index arrays
+ * rt_scene_from_mesh makes an rt_scene_host from arrays instead of a scene file, and rt_scene_face_index tells which
+ * input triangle each scene triangle is.  The presence of these symbols is the feature probe;
+ * RT_ABI_VERSION and every existing struct are unchanged.  No reference counterpart.
+ * Definition by equivalence -- the whole contract: the scene is byte for byte (every array and every scalar field of
+ * the rt_scene view: min_coord, inv_dimensions, the camera precompute, exposure, ...) the one rt_scene_load produces for
+ * the description's canonical scene file, whose lines are, in this order:
+ *   material m<k> diffuse r g b specular r g b emit r g b metallicity f roughness f ior f     per material, in order;
+ *   sky r g b                                                                                 if a sky is given;
+ *   sphere m<k> cx cy cz r                                                                    per sphere;
+ *   triangle m<k> <nine floats>                                                               per triangle, input order;
+ *   camera position x y z forward x y z up x y z fov deg                                      if a camera is given;
+ * every float printed so that it parses back to itself.  Width, height, spp, bounces and exposure come from opts
+ * (image_override, exposure_override), else the loader's defaults (1920 1080 1 3, exposure 0).  So: the triangle order
+ * and the node array are the reference build's; forward and up are normalised as the loader normalises them; the fov
+ * is (float)(deg * (pi / 180)) with the product in double; use_bvh = 0 gives the single leaf; bvh_device chooses the
+ * builder and does not change a bit.  Environment maps from memory are not offered (no query reads the sky).
+ * Refusals, all RT_E_INVALID, rt_last_error names the primitive, before either builder runs and, in the host entry,
+ * before any HIP call; in this order: a null mesh or out; a negative count; vertices NULL with triangle_count > 0
+ * (spheres NULL with sphere_count > 0); a soup whose vertex_count != 3 * triangle_count; a material-index array without
+ * a material table; material_count > 65535; sphere_count + triangle_count past int32; the loader's image-size rule; a
+ * sphere's, then a triangle's material index >= material_count (the first such); a vertex index < 0 or >= vertex_count
+ * (the smallest such triangle; before any finiteness check); then the loader's own rules with its own messages: a
+ * non-finite sphere; the first triangle in input order with a non-finite vertex coordinate or, its coordinates being
+ * finite, a non-finite centroid.  A non-finite vertex that no triangle references is not an error.
+ * rt_scene_from_mesh_device: vertices, indices and triangle_materials are device pointers on device
+ * opts->bvh_device, which must be >= 0 (else RT_E_INVALID); spheres, materials, camera and sky stay host memory.  The
+ * call is synchronous: it synchronises hip_stream (NULL = the null stream) before its first kernel reads the arrays,
+ * assembles, validates, builds and finalises on the device (csrc/mesh_ingest.hip, csrc/bvh_build.hip) and downloads
+ * the result.  What it returns is an ordinary host-owned rt_scene_host -- the scene does not stay on the device: the
+ * host twins (rt_scene_*) and rt_query_create's record packing read the arrays on the host.  Same result, same
+ * refusals and same messages as the host entry on the same numbers.
+ * rt_scene_face_index: a borrowed array of triangle_count int32, valid until rt_scene_free; entry j is the input index
+ * of scene triangle j, which is answer index sphere_count + j of every query.  Every rt_scene_host has it; for a
+ * file-loaded scene the input index is the triangle's position in the file (quads and ply faces counted as the
+ * triangles they become).  rt_scene_refit leaves it alone. */
+typedef struct { rt_vec3 position, forward, up; float vertical_fov_degrees; } rt_camera_desc;
+typedef struct {
+    const float   *vertices;  int32_t vertex_count;     /* 3 floats each */
+    const int32_t *indices;   int32_t triangle_count;   /* 3 per triangle; NULL = soup: triangle i is
+                                                           vertices 3i, 3i+1, 3i+2 and vertex_count == 3*triangle_count */
+    const uint16_t *triangle_materials;                 /* per triangle; NULL = all 0 */
+    const rt_sphere *spheres; int32_t sphere_count; const uint16_t *sphere_materials; /* NULL = all 0 */
+    const rt_material *materials; int32_t material_count; /* NULL/0 = one material: the loader's default
+                                                           (diffuse and specular 1,1,1, everything else 0) */
+    const rt_camera_desc *camera;                       /* NULL = what a file without a `camera` line gives */
+    const rt_vec3 *sky;                                 /* NULL = what a file without `sky` gives (one 0 texel) */
+} rt_mesh_desc;
+int rt_scene_from_mesh(const rt_mesh_desc *mesh, const rt_load_opts *opts, rt_scene_host **out);
+int rt_scene_from_mesh_device(const rt_mesh_desc *mesh, const rt_load_opts *opts, void *hip_stream, rt_scene_host **out);
+int rt_scene_face_index(const rt_scene_host *scene, const int32_t **index_out, int32_t *count_out);
+
 /* Replaces the bloom block of main (raytracing.cu:356-393, kernels :21-74): high-pass
  * (luminance > threshold), clamped box blur of `radius` horizontally then vertically,
  * add back.  fb is a host W*H*3 buffer, updated in place. */
